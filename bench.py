@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the fused HIP step path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (N=1): 65 536 independent games on one MI355X, both players driven by the uniform random
 policy, winning_score=15, serve="winner" (BASELINE.json configs: the per-GPU shard of the
@@ -11,15 +11,21 @@ columns and the two action vectors from HBM and writes state, both 35-dim observ
 rewards and the terminated flags.  The actions of all W+K steps are generated on device by the
 policy kernel BEFORE the timed region, so every input is resident in HBM when timing starts.
 
-Sequence of one measurement (every part replayed by the CPU oracle for the in-run parity check):
+Sequence of one measurement (with --full every part is replayed by the CPU oracle for the in-run parity check):
   reset -> BURN-IN (untimed; --burn-in frames of the on-device policy, so that the timed frames are
-  steady-state play: rounds ending, auto-resets, collisions) -> W warm-up launches -> K x ceil(2 048 / K)
-  launches captured in ONE hipGraph, every one on its OWN action slice (a cold tape: >= 2 048 distinct
-  slices = 1 GB streamed from HBM whatever K is, so that the driver's `--steps 20`, the default run and
-  every rocprofv3 trace measure one workload; `--action-tape hot` re-uses the K slices instead) -> one
-  untimed replay (graph upload + calibration) -> R timed replays, R chosen so that the timed region
-  lasts at least --min-time seconds whatever K is.  `steps` in the JSON line is K as given;
-  `timed_steps` = the launches actually timed; value = games * timed_steps / wall.
+  steady-state play: rounds ending, auto-resets, collisions) -> W warm-up launches -> the K timed launches
+  captured in ONE hipGraph (longer runs: a graph per 4 096 launches), cycling through their own action slices
+  (a cold tape: >= 2 048 distinct slices = 1 GB; `--action-tape hot` cycles through min(K, 4 096) slices) -> one
+  untimed replay of each graph (its upload) -> cold tape: 512 MiB of other bytes through the caches, the slices the
+  timed launches do not read first, then state and outputs read back in (flush_caches), so that they read their
+  actions from HBM whatever K is and the driver's
+  `--steps 20`, the default run and every rocprofv3 trace measure one workload -> ONE timed replay: exactly K timed
+  launches.  value = games * K / wall, ms_per_step = wall / K.  --dump-outputs DIR then writes what the last of
+  them left for its caller, and the state, as DIR/<name>.npy (dump_outputs).
+
+A plain run does only that and prints the line.  --full adds everything else the benchmark measures, each measured
+as before: the in-run oracle replay, the CPU baseline, the launch floor, the two-chain and other-tape measurements,
+the other BASELINE configs, formats and batch sizes, the k-frame launches, and the PMC-counted traffic figures.
 
 Multi-GPU (one rank per GPU; under torch.distributed.run as the driver launches it, or plain
 `python bench.py --gpus N`, which starts that launcher as a child process): weak scaling, rank r owns
@@ -29,6 +35,7 @@ gloo).  Timing: barrier + synchronize on both sides, MAX over ranks; `per_rank` 
 launch duration and rate, and the first and the last rank replay 1 024 of their games on the oracle.
 
 The single JSON line is FLAT (scalars and short strings only, < 8 KB: the driver's record drops nested objects) and carries
+(the traffic figures, the per-measurement scalars and cpu_baseline with --full only)
   roofline     -- algorithmic HBM bytes per launch (649 B/game-step) / average launch duration measured with
                   HIP events on the launch stream over the timed region, against 8 TB/s (`frac`: a CONTRACT-bytes
                   figure, see `frac_basis`); the same from the wall clock `value` is computed from (`frac_wall`); and
@@ -77,6 +84,8 @@ INFINITY_CACHE_BYTES = 256 << 20
 ACTION_SEED = 1
 BURN_SEED = 2
 GRAPH_MIN_LAUNCHES = 2048          # a replay must dwarf its own host-side launch cost (10-16 us)
+GRAPH_MAX_LAUNCHES = 8192          # a timed pass up to this long is one graph; a longer one replays a graph per ring lap
+TAPE_RING_MAX = 4096               # distinct action slices the warm-up and the timed launches each cycle through at most
 WRAPPER_TABLE = (0.0, -0.01, 0.0, 0.01, 0.0, 0.01, 0.0, -0.01)
 
 
@@ -89,7 +98,6 @@ def parse_args():
     ap.add_argument("--launch", choices=["graph", "cabi", "api"], default="graph",
                     help="graph: the K launches captured once in a hipGraph and replayed; cabi: K direct "
                          "C-ABI calls; api: K env.step() calls")
-    ap.add_argument("--min-time", type=float, default=0.25, help="minimum duration of the timed region (s)")
     ap.add_argument("--burn-in", type=int, default=4096, help="untimed frames of random play before warm-up")
     ap.add_argument("--p2-computer", action="store_true", help="config 3: rule-based AI on player 2")
     ap.add_argument("--p1-computer", action="store_true", help="rule-based AI on player 1 (not a BASELINE config)")
@@ -121,6 +129,14 @@ def parse_args():
                          "distinct slices = 1 GB streamed from HBM, whatever --steps is -- the default and what every profile "
                          "under profiles/ ran) or the K slices are re-used out of the caches (hot: what a policy that has "
                          "just written its actions presents); the other one is measured beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the in-run oracle replay, the CPU baseline, the launch "
+                         "floor, the two-chain and other-tape measurements, configs 2/3/5 and the other formats and batch "
+                         "sizes, the k-frame launches and the PMC-counted traffic of profiles/traffic.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (both observations, both rewards, the "
+                         "terminated flags and the state) as DIR/<name>.npy in float32 / float64; above 64 MB a fixed, "
+                         "seeded sample of the games.  With N ranks: rank 0's games only")
     ap.add_argument("--configs-out", default=None,
                     help="file for the verbose blocks (every config's full entry, --extra, per-rank rows, what the regimes "
                          "mean); without it they go to stderr as one line.  The stdout line stays below 8 KB")
@@ -168,13 +184,44 @@ def graph_repeats(steps):
     return max(1, math.ceil(GRAPH_MIN_LAUNCHES / steps))
 
 
-def run_gpu(env, acts, warmup, steps, launch, min_time):
-    """W untimed launches, then the timed unit -- `acts.shape[0] - warmup` launches, one per action slice of the tape
-    behind the warm-up slices (a multiple of K: K itself on a hot tape, K x graph_repeats(K) distinct slices on a cold
-    one) -- repeated until the timed region lasts >= min_time.
+def laps(count, ring, base=0):
+    """`count` launches cycling through `ring` action slices from slice `base` on, as (first slice, launches) runs in
+    the order they execute (slice t holds Philox step t of ACTION_SEED: the oracle replays the same runs)."""
+    runs = [(base, ring)] * (count // ring)
+    return runs + ([(base, count % ring)] if count % ring else [])
 
-    Returns dict(wall, event_ms, timed_steps, passes): `passes` = how many times the unit's action sequence ran in
-    total (untimed calibration pass included) -- what the oracle has to replay."""
+
+FLUSH_BYTES = 2 * INFINITY_CACHE_BYTES
+
+
+def flush_caches(spare, device, resident=()):
+    """Move FLUSH_BYTES of other data through the L2s and the Infinity Cache, so that nothing a launch touched before
+    stays resident (a line stays only while it plus every byte loaded or stored since its last use fits in 256 MiB,
+    MI355X_MICROARCH.md): a read of `spare` -- the tape's slices the timed launches never read -- topped up by
+    writing a scratch buffer when those hold fewer bytes.  Then the `resident` tensors are read back in: the working
+    set every launch re-touches (state, observations, rewards, flags) is where steady play keeps it, and only the
+    action slices come from HBM.  On the current stream, outside every timed region."""
+    done = spare.numel() * spare.element_size()
+    if done:
+        spare.sum(dtype=torch.int64)
+    if done < FLUSH_BYTES:
+        torch.empty(FLUSH_BYTES - done, dtype=torch.uint8, device=device).zero_()
+    for t in resident:
+        t.sum(dtype=torch.int64)
+
+
+def run_gpu(env, acts, warmup, steps, ring, launch, min_time=None, cold=False):
+    """W untimed launches (the tape's first w = min(W, TAPE_RING_MAX) slices, cycled), then the timed pass: `steps`
+    launches, launch i on slice w + (i mod ring) -- the `ring` slices behind the warm-up ones, cycled.
+
+    min_time None: the pass is timed once -- exactly `steps` timed launches; with graph launches every distinct graph
+    is replayed once untimed first (its upload).  cold (with min_time None): then, still untimed, flush_caches() --
+    the upload and the tape's generation have just touched the timed slices, and the timed launches must find them in
+    HBM, whatever K is.  min_time given: one untimed pass (calibration and upload), then the pass R times, R chosen so
+    that the timed region lasts >= min_time.
+
+    Returns dict(wall, event_ms, timed_steps, runs): `runs` = every launch since the warm-up began as (first slice,
+    launches) runs in order -- what the oracle has to replay."""
     raw = env.unwrapped
     lib = _native.load()
     n = raw.num_envs
@@ -189,58 +236,72 @@ def run_gpu(env, acts, warmup, steps, launch, min_time):
         cfg_typed = _native.PzConfig.from_buffer_copy(raw._cfg)
         cfg_typed.action_format = _native.ACTION_FORMATS[str(acts.dtype).replace("torch.", "")]
         cfg = C.byref(cfg_typed)
+    warm_ring = acts.shape[0] - ring
+    assert 0 < ring and warm_ring == min(warmup, TAPE_RING_MAX)
+    if launch == "api":
+        names = raw.possible_agents
+        # the per-step action dicts a policy would hand over (views built outside the timed loop)
+        feed = [{names[0]: acts[t, 0], names[1]: acts[t, 1]} for t in range(acts.shape[0])]
 
-    def launch_range(t_lo, t_hi, stream):
+    def launch_run(t0, count, stream):
         s = stream.cuda_stream
-        for t in range(t_lo, t_hi):
+        if launch == "api":
+            step = env.step
+            for t in range(t0, t0 + count):
+                step(feed[t])
+            return
+        for t in range(t0, t0 + count):
             rc = lib.pz_step(st, n, raw._stride, cfg, a_ptr + t * a_stride, a_ptr + t * a_stride + n * elem, o1, o2, r1, r2, tm,
                              None, tables, s)
             if rc:
                 _native.check(rc, "pz_step")
 
     stream = torch.cuda.Stream(device=raw.device)
-    unit_steps = acts.shape[0] - warmup  # launches per timed unit = action slices behind the warm-up ones
-    assert unit_steps >= steps and unit_steps % steps == 0
+    timed_runs = laps(steps, ring, warm_ring)
+    runs = laps(warmup, warm_ring) if warmup else []
     with torch.cuda.stream(stream):
-        if launch == "api":
-            names = raw.possible_agents
-            # the per-step action dicts a policy would hand over (views built outside the timed loop)
-            feed = [{names[0]: acts[t, 0], names[1]: acts[t, 1]} for t in range(warmup + unit_steps)]
+        for t0, count in runs:
+            launch_run(t0, count, stream)
+        if launch == "graph":
+            stream.synchronize()
+            # the whole pass in one graph; a longer one as a graph per lap of the ring and one for the remainder
+            chunks = [tuple(timed_runs)] if steps <= GRAPH_MAX_LAUNCHES else [(run,) for run in timed_runs]
+            graphs = {}
+            for chunk in chunks:
+                if chunk not in graphs:
+                    graphs[chunk] = torch.cuda.CUDAGraph()
+                    # thread_local: the RCCL watchdog thread of a multi-rank run may poll events while we capture
+                    with torch.cuda.graph(graphs[chunk], stream=stream, capture_error_mode="thread_local"):
+                        for t0, count in chunk:
+                            launch_run(t0, count, torch.cuda.current_stream(raw.device))
+                    # (capture records the launches without running them)
+            plan = [graphs[chunk] for chunk in chunks]
 
             def unit():
-                step = env.step
-                for t in range(warmup, warmup + unit_steps):
-                    step(feed[t])
-            for t in range(warmup):
-                env.step(feed[t])
-        else:
-            launch_range(0, warmup, stream)
-            if launch == "graph":
-                graph_launches = max(unit_steps, steps * graph_repeats(steps))
-                stream.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                # thread_local: the RCCL watchdog thread of a multi-rank run may poll events while we capture
-                with torch.cuda.graph(graph, stream=stream, capture_error_mode="thread_local"):
-                    for _ in range(graph_launches // unit_steps):  # (hot tape: the K slices again and again)
-                        launch_range(warmup, warmup + unit_steps, torch.cuda.current_stream(raw.device))
-                # (capture records the launches without running them)
-                unit_passes = graph_launches // unit_steps
-
-                def unit():
+                for graph in plan:
                     graph.replay()
-            else:
-                unit_passes = 1
-
-                def unit():
-                    launch_range(warmup, warmup + unit_steps, stream)
-        # untimed calibration pass (also the graph upload)
-        stream.synchronize()
-        t0 = time.perf_counter()
-        unit()
-        stream.synchronize()
-        est = time.perf_counter() - t0
-        reps = max(1, math.ceil(min_time / max(est, 1e-6)))
-        reps = int(dist.all_reduce_max(reps, device=dist.collective_device(raw.device)))  # same count on every rank
+            if min_time is None:
+                for chunk, graph in graphs.items():  # the upload of every graph, untimed
+                    graph.replay()
+                    runs += chunk
+        else:
+            def unit():
+                for t0, count in timed_runs:
+                    launch_run(t0, count, stream)
+        if cold and min_time is None:
+            flush_caches(acts[warm_ring + min(steps, ring):], raw.device,
+                         (raw._state_buf, *raw._obs, *raw._rew_raw, raw._term_u8))
+        reps = 1
+        if min_time is not None:
+            # untimed calibration pass (also the graph upload)
+            stream.synchronize()
+            t0 = time.perf_counter()
+            unit()
+            stream.synchronize()
+            est = time.perf_counter() - t0
+            runs += timed_runs
+            reps = max(1, math.ceil(min_time / max(est, 1e-6)))
+            reps = int(dist.all_reduce_max(reps, device=dist.collective_device(raw.device)))  # same count on every rank
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
         stream.synchronize()
@@ -255,12 +316,10 @@ def run_gpu(env, acts, warmup, steps, launch, min_time):
         dist.barrier()
         wall = time.perf_counter() - t0
         ev_ms = ev0.elapsed_time(ev1)
-    if launch == "api":
-        unit_passes = 1
-    passes = unit_passes * (reps + 1)
-    raw.steps_done = warmup + unit_steps * passes
-    return {"wall": wall, "event_ms": ev_ms, "timed_steps": unit_steps * unit_passes * reps, "passes": passes,
-            "replays": reps, "launches_per_replay": unit_steps * unit_passes, "unit_steps": unit_steps}
+    runs += timed_runs * reps
+    raw.steps_done = sum(count for _, count in runs)
+    return {"wall": wall, "event_ms": ev_ms, "timed_steps": steps * reps, "runs": runs, "replays": reps,
+            "launches_per_replay": steps}
 
 
 def usable_cores(requested: int) -> int:
@@ -283,8 +342,8 @@ def oracle_config(po, raw, p1_computer, p2_computer, wrappers, base):
 
 
 def oracle_parity(raw, seq, p1_computer, p2_computer, wrappers, lanes, cores):
-    """Replay burn-in + warm-up + every pass of the K-step sequence on the first `lanes` games with the
-    CPU oracle and compare the full state bit for bit."""
+    """Replay burn-in + every launch since the warm-up began (`seq["runs"]`, in order) on the first `lanes` games with
+    the CPU oracle and compare the full state bit for bit."""
     from oracle import pz_oracle as po
 
     po.build()
@@ -293,12 +352,10 @@ def oracle_parity(raw, seq, p1_computer, p2_computer, wrappers, lanes, cores):
     chk.reset()
     if seq["burn_in"]:
         chk.rollout_random(BURN_SEED, 0, seq["burn_in"])
-    if seq["warmup"]:
-        chk.rollout_random(ACTION_SEED, 0, seq["warmup"])
-    for _ in range(seq["passes"]):
-        chk.rollout_random(ACTION_SEED, seq["warmup"], seq["unit_steps"])
+    for t0, count in seq["runs"]:
+        chk.rollout_random(ACTION_SEED, t0, count)
     gpu_state = raw.read_state()[:, :k].cpu().numpy()
-    total = seq["burn_in"] + seq["warmup"] + seq["passes"] * seq["unit_steps"]
+    total = seq["burn_in"] + sum(count for _, count in seq["runs"])
     return {"parity_lanes_checked": k, "parity_steps_checked": total,
             "parity_bit_exact": bool((gpu_state == chk.state).all())}
 
@@ -352,14 +409,20 @@ def cpu_baseline(args, raw_gpu, p2_computer, wrappers):
 def measure(args, shard, device, *, num_envs=None, p2_computer=False, wrappers=False, launch=None, steps=None,
             warmup=None, burn=None, min_time=None, check_lanes=0, flight_tables=True, state_format="int32", obs16=False,
             validate_actions=False, tape="cold", action_dtype=torch.int32):
-    """One timed measurement of the single-frame launch.  tape = "cold": every launch of the timed unit reads its own
-    action slice (K x graph_repeats(K) distinct slices behind the warm-up ones: >= 1 GB at 65 536 games, streamed from
-    HBM); "hot": the K slices are re-used."""
+    """One timed measurement of the single-frame launch.
+
+    min_time None (the headline): exactly `steps` timed launches.  tape = "cold": they cycle through
+    max(2 048, min(K, 4 096)) distinct action slices behind the warm-up ones (graph launches; min(K, 4 096) with the
+    others), and right before the timed region 512 MiB of other bytes -- the slices they do not read first -- go
+    through the caches (flush_caches), so the first lap of slices comes from HBM whatever K is, and a lap of 2 048
+    slices (1 GB at 65 536 games) is more than the Infinity Cache holds; "hot": through min(K, 4 096) slices, which
+    the graph's upload replay has just read.
+    min_time given (the other measurements of --full): the K-step sequence, as K x graph_repeats(K) launches on as many
+    distinct slices (cold) or on the K slices again and again (hot), repeated until the timed region lasts >= min_time."""
     num_envs = args.num_envs if num_envs is None else num_envs
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     burn = args.burn_in if burn is None else burn
-    min_time = args.min_time if min_time is None else min_time
     launch = args.launch if launch is None else launch
     env = make_env(shard, device, num_envs=num_envs, p1_computer=args.p1_computer, p2_computer=p2_computer,
                    wrappers=wrappers, flight_tables=flight_tables, state_format=state_format, obs16=obs16,
@@ -367,12 +430,19 @@ def measure(args, shard, device, *, num_envs=None, p2_computer=False, wrappers=F
     raw = env.unwrapped
     env.reset()
     burn_in(raw, burn)
-    unit_steps = steps * graph_repeats(steps) if (tape == "cold" and launch == "graph") else steps
-    acts = pregenerate_actions(raw, warmup + unit_steps)
+    if min_time is None:
+        pass_steps = steps
+        ring = min(steps, TAPE_RING_MAX)
+        if tape == "cold" and launch == "graph":
+            ring = max(GRAPH_MIN_LAUNCHES, ring)
+    else:
+        pass_steps = steps * graph_repeats(steps) if launch == "graph" else steps
+        ring = pass_steps if (tape == "cold" and launch == "graph") else steps
+    acts = pregenerate_actions(raw, min(warmup, TAPE_RING_MAX) + ring)
     if action_dtype != torch.int32:
         acts = acts.to(action_dtype)  # (outside every timed region: the tape as a policy of that dtype would leave it)
     torch.cuda.synchronize(device)
-    run = run_gpu(env, acts, warmup, steps, launch, min_time)
+    run = run_gpu(env, acts, warmup, pass_steps, ring, launch, min_time, cold=tape == "cold")
     cdev = dist.collective_device(device)  # counters live on the GPU under nccl (RCCL), on the CPU under gloo
     wall = dist.all_reduce_max(run["wall"], device=cdev)
     n_total, = dist.all_reduce_sum([raw.num_envs], device=cdev)
@@ -394,11 +464,43 @@ def measure(args, shard, device, *, num_envs=None, p2_computer=False, wrappers=F
     res["frac"] = res["achieved_GBps"] / HBM_PEAK_GBPS
     res["frac_wall"] = alg / (res["wall_us_per_step"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
     if check_lanes and not args.no_cpu:  # (the caller says which ranks check)
-        seq = {"burn_in": burn, "warmup": warmup, "unit_steps": run["unit_steps"], "passes": run["passes"]}
+        seq = {"burn_in": burn, "runs": run["runs"]}
         res.update(oracle_parity(raw, seq, args.p1_computer, p2_computer, wrappers, check_lanes,
                                  usable_cores(args.cpu_threads)))
     del acts
     return res
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(raw, out_dir):
+    """What the last timed launch left for its caller -- both observations, both rewards, the terminated flags -- and
+    the state it stepped, as out_dir/<name>.npy (float32; the state float64, which holds every int32 word exactly).
+    Above DUMP_LIMIT_BYTES the same fixed, seeded sample of the games (sorted indices in games.npy) from every array.
+    main() calls it on rank 0 only: with N ranks the files hold rank 0's shard (global games 0 .. num_envs - 1)."""
+    import numpy as np
+
+    torch.cuda.synchronize(raw.device)
+    arrays = {
+        "obs_player_1": raw._obs[0].float(), "obs_player_2": raw._obs[1].float(),
+        "reward_player_1": raw._rewards()[0].float(), "reward_player_2": raw._rewards()[1].float(),
+        "terminated": raw._term_u8.float(), "state": raw.read_state().double().t(),  # [games, 44]
+    }
+    n = raw.num_envs
+    per_game = sum(a[0].numel() * a.element_size() for a in arrays.values())
+    games = None
+    if n * per_game > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 8 * n) // per_game  # (the index array itself counted at its full length)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: {n} games do not fit a sample below {DUMP_LIMIT_BYTES} bytes")
+        games = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy()
+        np.save(out_dir / f"{name}.npy", a if games is None else a[games])
+    if games is not None:
+        np.save(out_dir / "games.npy", games.astype(np.float64))
 
 
 def measure_launch_floor(device, num_envs, frame_steps=102, min_time=0.05):
@@ -864,10 +966,10 @@ BOUND_DETAIL = {
 }
 
 
-def fractions(r, num_envs, key):
-    """The roofline figures of one single-frame measurement: on the algorithmic (contract) bytes and on the
-    counter-measured bytes of profiles/traffic.json."""
-    traffic = load_traffic(key, num_envs)
+def fractions(r, num_envs, key, with_traffic=True):
+    """The roofline figures of one single-frame measurement: on the algorithmic (contract) bytes and (with_traffic) on
+    the counter-measured bytes of profiles/traffic.json."""
+    traffic = load_traffic(key, num_envs) if with_traffic else None
     launch_s = r["launch_us"] * 1e-6
     reg = regime(num_envs)
     return {"frac": r["frac"], "frac_wall": r["frac_wall"], "traffic": traffic,
@@ -904,7 +1006,7 @@ def relaunch_with_ranks(args):
 def main():
     args = parse_args()
     if int(os.environ.get("RANK", "0")) == 0:
-        ensure_built(with_oracle=not args.no_cpu)
+        ensure_built(with_oracle=args.full and not args.no_cpu)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_with_ranks(args))
     one_device = os.environ.get("PZ_BENCH_ONE_DEVICE") == "1"  # rehearsal: every rank on cuda:0 of a 1-GPU box
@@ -932,12 +1034,15 @@ def main():
         print(json.dumps(out), flush=True)
         return
 
-    # the in-run oracle replay: all of it with one rank; with N ranks the first and the last rank check 1 024 lanes each
+    # --full: the in-run oracle replay, all of it with one rank; with N ranks the first and the last rank check 1 024
+    # lanes each
     check_lanes = args.check_lanes if single else (min(1024, args.check_lanes) if rank in (0, world - 1) else 0)
     main_res = measure(args, shard, device, p2_computer=args.p2_computer, wrappers=args.wrappers,
-                       check_lanes=check_lanes, flight_tables=tables, state_format=args.state_format, obs16=args.int16_obs,
-                       tape=args.action_tape, action_dtype=action_dtype)
+                       check_lanes=check_lanes if args.full else 0, flight_tables=tables, state_format=args.state_format,
+                       obs16=args.int16_obs, tape=args.action_tape, action_dtype=action_dtype)
     raw_main = main_res.pop("raw")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(raw_main, Path(args.dump_outputs))
     # every rank's own figures (a straggler GPU is invisible in the MAX-over-ranks wall clock alone)
     parity = main_res.get("parity_bit_exact")
     rows = dist.all_gather_rows([rank, main_res["launch_us"], raw_main.num_envs * main_res["timed_steps"] /
@@ -945,8 +1050,9 @@ def main():
                                  raw_main.env_id_base], device=cdev)
     per_rank = [{"rank": int(r[0]), "env_id_base": int(r[4]), "launch_us": r[1], "value": r[2],
                  "parity_bit_exact": None if r[3] < 0 else bool(r[3])} for r in rows]
+    full = single and args.full  # everything beside the headline (one rank only)
     cpu = None
-    if single and not args.no_cpu:
+    if full and not args.no_cpu:
         cpu = cpu_baseline(args, raw_main, args.p2_computer, args.wrappers)
         for k in ("parity_bit_exact", "parity_lanes_checked", "parity_steps_checked"):
             cpu[k] = main_res.get(k)
@@ -954,7 +1060,7 @@ def main():
 
     # what the headline launch is made of, with the same batch size (the plain int32 contract only)
     launch_floor = launch_floor_error = None
-    if single and args.state_format == "int32" and not args.int16_obs and args.launch == "graph":
+    if full and args.state_format == "int32" and not args.int16_obs and args.launch == "graph":
         try:
             launch_floor = measure_launch_floor(device, args.num_envs)
         except Exception as exc:  # noqa: BLE001 - a diagnostic beside the line, never a reason to lose the line
@@ -962,7 +1068,7 @@ def main():
             print(f"[bench] launch_floor skipped: {launch_floor_error}", file=sys.stderr, flush=True)
     # the batch as two independent 32 768-game chains (beside the headline; a diagnostic, never a reason to lose the line)
     pipelined = None
-    if single and not args.no_configs and args.state_format == "int32" and not args.int16_obs:
+    if full and not args.no_configs and args.state_format == "int32" and not args.int16_obs:
         try:
             pipelined = measure_two_chains(args, shard, device, p2_computer=args.p2_computer)
         except Exception as exc:  # noqa: BLE001
@@ -971,7 +1077,7 @@ def main():
     # the same workload on the other kind of action tape (cold: every launch its own slice, >= 1 GB streamed from HBM;
     # hot: K slices re-used out of the caches, what a policy that has just written its actions presents)
     other_tape = None
-    if single and not args.no_configs:
+    if full and not args.no_configs:
         other = "hot" if args.action_tape == "cold" else "cold"
         o_steps = min(args.steps, 20) if other == "hot" else args.steps
         r = measure(args, shard, device, p2_computer=args.p2_computer, wrappers=args.wrappers, flight_tables=tables,
@@ -982,7 +1088,7 @@ def main():
                       "value": r["value"], "launch_us": r["launch_us"], "frac": r["frac"]}
 
     configs = {}
-    if single and not args.no_configs:
+    if full and not args.no_configs:
         # the other single-GPU BASELINE configs, each timed like the headline (shorter) and oracle-checked
         sub = dict(steps=1000, warmup=100, burn=2048, min_time=0.1, check_lanes=1024, launch="graph")
         specs = {
@@ -1113,7 +1219,7 @@ def main():
         alg_bytes = main_res["algorithmic_bytes_per_launch"]
         wl = traffic_key(args.num_envs, args.p2_computer, args.wrappers, tables, args.state_format, args.int16_obs,
                          args.p1_computer)
-        fr = fractions(main_res, args.num_envs, wl)
+        fr = fractions(main_res, args.num_envs, wl, with_traffic=args.full)
         tstat = _TRAFFIC_STATUS.get(wl, {})
         checked = [p for p in per_rank if p["parity_bit_exact"] is not None]
         workload = (f"{args.num_envs} games/GPU, random policy both players (Philox stream in HBM), winning_score=15, "
@@ -1139,8 +1245,8 @@ def main():
             "config": {
                 "workload": workload,
                 "num_envs_per_gpu": args.num_envs, "num_envs_total": main_res["n_total"],
-                # cold: every launch of a graph replay reads its own action slice (>= 2 048 distinct slices, streamed from
-                # HBM whatever --steps is); hot: the K slices re-used out of the caches
+                # cold: the timed launches cycle through >= 2 048 distinct action slices, the caches flushed right
+                # before the timed region (out of HBM whatever --steps is); hot: through min(K, 4 096) slices
                 "action_tape": main_res["action_tape"], "action_tape_bytes": main_res["action_tape_bytes"],
                 "launch": args.launch,
                 "kernel": kernel_name(args.num_envs, args.p2_computer or args.p1_computer, tables != "none",
@@ -1184,6 +1290,9 @@ def main():
             },
         }
         roof = out["roofline"]
+        if not args.full:  # (profiles/traffic.json was not consulted: no counted-bytes figures, stale or not)
+            for k in ("traffic", "traffic_key", "traffic_build_id", "traffic_stale", "traffic_check", "frac_traffic"):
+                roof.pop(k)
         if world > 1:
             out["per_rank"] = per_rank  # (N rows: small; with one rank the flat figures above say it all)
 

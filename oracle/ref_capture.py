@@ -19,6 +19,7 @@ TEST INFRASTRUCTURE: not imported by the product.
 from __future__ import annotations
 
 import json
+import struct
 import sys
 import types
 from pathlib import Path
@@ -777,6 +778,126 @@ DIGEST_RUNS = [
 ]
 
 
+# tests/test_oracle_vs_reference.py: the reference on seeds of its own, beside the fixtures above (stored as live_*.npz so
+# that the tests run wherever the reference checkout is not)
+LIVE_TABLE = [0.0, -0.01, 0.0, 0.01, 0.0, 0.01, 0.0, -0.01]
+LIVE_RUNS = [
+    # name, env_kwargs, wrappers: 6 lanes x 2 500 steps each
+    ("human_human", dict(winning_score=5, serve="winner"), None),
+    ("p1_computer_random_serve", dict(winning_score=3, serve="random", is_player1_computer=True), None),
+    ("both_computer_alternate", dict(winning_score=2, serve="alternate", is_player1_computer=True,
+                                     is_player2_computer=True), None),
+    ("wrapper_stack", dict(winning_score=2, is_player2_computer=True),
+     dict(stack=[["SimplifyAction", {}], ["RecordEpisodeStatistics", {}],
+                 ["RewardByBallPosition", dict(additional_reward=LIVE_TABLE)],
+                 ["RewardInNormalState", dict(reward=0.03125)], ["NormalizeObservation", {}]])),
+]
+LIVE_PLANTED = [dict(winning_score=4), dict(winning_score=2, is_player1_computer=True, is_player2_computer=True),
+                dict(winning_score=3, is_player2_computer=True, serve="random"),
+                dict(winning_score=3, is_player1_computer=True, serve="alternate")]
+LIVE_DRAW_LISTS = 400
+
+
+def capture_live(name, kw, wr):
+    return capture(name, 6, 2500, seed=424242, action_seed=31, env_id_base=99, env_kwargs=kw, wrappers=wr, full=True)
+
+
+def capture_live_planted(k):
+    """Fresh planted states on configuration LIVE_PLANTED[k]: (random attributes, fast-ball corners)."""
+    kw = LIVE_PLANTED[k]
+    return (capture_planted_random("live", 1500, seed=31337, action_seed=5, env_id_base=7700, env_kwargs=kw, frames=10,
+                                   plant_seed=2024),
+            capture_planted("live", seed=31338, action_seed=6, env_id_base=8800, env_kwargs=kw, frames=12))
+
+
+def capture_live_draw_lists(count: int = LIVE_DRAW_LISTS) -> dict:
+    """render() of the reference on `count` random planted states (every pose / mirroring / score digit / hyper ball,
+    balls partly or wholly off screen).  Recorded per render: the 44 state words and the scenery words it was drawn
+    from, and the blits it issued behind the static background as (file, mirrored, x, y, width, height) rows -- the
+    punch effect left out -- with the sprite sizes (oracle/render_oracle.py's sprite order)."""
+    from oracle import render_oracle as ro
+
+    files = ro.sprite_files()
+    rng = np.random.default_rng(77)
+    states, scenery, rows, offsets = [], [], [], [0]
+    for i in range(count):
+        env, raw, shim = make_reference_env(5, 300 + i, None, render_mode="rgb_array", winning_score=15)
+        env.reset()
+        for pl in (raw.physics.player1, raw.physics.player2):
+            pl.state = int(rng.integers(0, 5))
+            pl.frame_number = int(rng.integers(0, 5 if pl.state < 3 else (2 if pl.state == 3 else 1)))
+            pl.diving_direction = int(rng.integers(-1, 2))
+            pl.y = int(rng.integers(108, 245))
+        b = raw.physics.ball
+        b.x, b.y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
+        b.previous_x, b.previous_y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
+        b.previous_previous_x, b.previous_previous_y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
+        b.is_power_hit = bool(rng.integers(0, 2))
+        b.fine_rotation = int(rng.integers(0, 51))
+        b.rotation = b.fine_rotation // 10
+        raw.scores = [int(rng.integers(0, 16)), int(rng.integers(0, 16))]
+        raw.render()
+        blits = raw.screen.blits[BACKGROUND_BLITS:]
+        rows += [(files.index(f), int(flip), x, y, w, h) for (f, flip, scaled), x, y, w, h in blits if f != "ball_punch.png"]
+        offsets.append(len(rows))
+        states.append(extract_state(raw, shim))
+        scenery.append(extract_scenery(raw))
+    sizes = [_png_size(REFERENCE_ROOT / "pikazoo" / "env" / "img" / f) for f in files]
+    meta = dict(count=count, seed=77)
+    return dict(states=np.array(states, np.int64), scenery=np.array(scenery, np.int32),
+                blits=np.array(rows, np.int32).reshape(-1, 6), offsets=np.array(offsets, np.int64),
+                sizes=np.array(sizes, np.int32), meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
+
+
+def capture_png_layout() -> dict:
+    """How the reference's PNG assets are laid out (not their pixels): per file its IHDR fields, the sizes of its IDAT
+    chunks and the filter type of every scanline.  tests/test_render_cpu.py encodes PNGs of exactly that layout."""
+    import zlib
+
+    img = REFERENCE_ROOT / "pikazoo" / "env" / "img"
+    names, ihdr, idat_sizes, idat_offsets, filters, filter_offsets = [], [], [], [0], [], [0]
+    for path in sorted(img.glob("*.png")):
+        b = path.read_bytes()
+        i, idat = 8, []
+        while i < len(b):
+            n = int.from_bytes(b[i:i + 4], "big")
+            kind, body = b[i + 4:i + 8], b[i + 8:i + 8 + n]
+            if kind == b"IHDR":
+                w, h, depth, color, comp, filt, interlace = struct.unpack(">IIBBBBB", body)
+            elif kind == b"IDAT":
+                idat.append(body)
+            i += 12 + n
+        assert (depth, color, interlace) == (8, 6, 0), path  # 8-bit RGBA, not interlaced: what render.py reads
+        raw = zlib.decompress(b"".join(idat))
+        names.append(path.name)
+        ihdr.append((w, h, depth, color, comp, filt, interlace))
+        idat_sizes += [len(c) for c in idat]
+        idat_offsets.append(len(idat_sizes))
+        filters += [raw[y * (1 + 4 * w)] for y in range(h)]
+        filter_offsets.append(len(filters))
+    meta = dict(names=names)
+    return dict(ihdr=np.array(ihdr, np.int64), idat_sizes=np.array(idat_sizes, np.int64),
+                idat_offsets=np.array(idat_offsets, np.int64), filters=np.array(filters, np.uint8),
+                filter_offsets=np.array(filter_offsets, np.int64),
+                meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
+
+
+def write_live_fixtures(only=None):
+    """tests/golden/live_*.npz and reference_png_layout.npz (tests/test_oracle_vs_reference.py, tests/test_render_cpu.py)."""
+    for name, kw, wr in LIVE_RUNS:
+        if only in (None, f"live_{name}"):
+            np.savez_compressed(GOLDEN / f"live_{name}.npz", **capture_live(name, kw, wr))
+    for k in range(len(LIVE_PLANTED)):
+        if only in (None, f"live_planted_{k}"):
+            rnd, fast = capture_live_planted(k)
+            np.savez_compressed(GOLDEN / f"live_planted_{k}.npz", **{f"random_{key}": v for key, v in rnd.items()},
+                                **{f"fast_{key}": v for key, v in fast.items()})
+    if only in (None, "live_draw_lists"):
+        np.savez_compressed(GOLDEN / "live_draw_lists.npz", **capture_live_draw_lists())
+    if only in (None, "reference_png_layout"):
+        np.savez_compressed(GOLDEN / "reference_png_layout.npz", **capture_png_layout())
+
+
 def main(argv=None):
     import argparse
     import time
@@ -838,6 +959,7 @@ def main(argv=None):
         np.savez_compressed(GOLDEN / f"{name}.npz", **data)
         print(f"{name}: {len(periods)} lanes x {steps} steps, {len(data['frame_lane'])} frames "
               f"{(GOLDEN / (name + '.npz')).stat().st_size / 1e3:.0f} kB")
+    write_live_fixtures(args.only)
     if not args.skip_digests:
         for k, (name, lanes, steps, kw, wr) in enumerate(DIGEST_RUNS):
             if args.only and args.only != name:

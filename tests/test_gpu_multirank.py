@@ -98,13 +98,13 @@ def test_two_ranks_through_the_hip_path_equal_the_single_batch(tmp_path):
 
 
 def test_bench_with_two_ranks_prints_the_aggregate_line():
-    """Plain `python bench.py --gpus 2`: bench.py starts its two ranks itself (a child torch.distributed.run, what the
+    """`python bench.py --gpus 2 --full`: bench.py starts its two ranks itself (a child torch.distributed.run, what the
     driver would have started); both share cuda:0 (PZ_BENCH_ONE_DEVICE) and gloo stands in for RCCL.  value must be
     the whole-job aggregate, every rank reports its own figures, and the first and the last rank replay their games
     on the oracle."""
     env = dict(os.environ, PZ_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "64", "--warmup", "8", "--burn-in", "128",
-           "--min-time", "0.05", "--dist-backend", "gloo", "--cpu-threads", "4"]
+           "--full", "--dist-backend", "gloo", "--cpu-threads", "4"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(REPO))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -112,7 +112,7 @@ def test_bench_with_two_ranks_prints_the_aggregate_line():
     # gloo carried the counters: that is said, and not counted as RCCL ranks
     assert out["n_gpus"] == 2 and out["ranks"] == 2 and out["rccl_ranks"] == 0 and out["dist_backend"] == "gloo"
     assert out["config"]["num_envs_total"] == 2 * 65536 and out["scaling"] == "weak"
-    assert out["timed_steps"] >= 64 and out["timed_seconds"] >= 0.05
+    assert out["timed_steps"] == 64 and out["timed_seconds"] > 0  # --steps sets the number of timed steps
     per_step_s = out["ms_per_step"] * 1e-3
     assert np.isclose(out["value"], 2 * 65536 / per_step_s, rtol=1e-6)
     assert "configs" not in out and "cpu_baseline" not in out  # single-GPU extras stay off for N > 1
@@ -122,7 +122,7 @@ def test_bench_with_two_ranks_prints_the_aggregate_line():
 
 
 def test_bench_with_four_ranks_on_one_device_shards_like_config_4():
-    """`python bench.py --gpus 4 --num-envs 65536` -- BASELINE config 4's per-rank shard at the largest rank count the
+    """`python bench.py --gpus 4 --num-envs 65536 --full` -- BASELINE config 4's per-rank shard at the largest rank count the
     one-GPU box allows (six processes may have its card open: four ranks, their launcher and this one -- five ranks were
     killed by the box's process guard; the eight-rank integers are covered over gloo on the CPU,
     tests/test_cabi_and_host.py): `per_rank` has a row per rank, rank r's games start at r * 65 536 (the first and the
@@ -130,7 +130,7 @@ def test_bench_with_four_ranks_on_one_device_shards_like_config_4():
     ranks = 4
     env = dict(os.environ, PZ_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", str(ranks), "--num-envs", "65536", "--steps", "16", "--warmup", "4",
-           "--burn-in", "64", "--min-time", "0.02", "--dist-backend", "gloo", "--cpu-threads", "2", "--no-configs",
+           "--burn-in", "64", "--full", "--dist-backend", "gloo", "--cpu-threads", "2", "--no-configs",
            "--check-lanes", "256"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(REPO))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -161,26 +161,27 @@ def test_bench_under_the_drivers_launcher_and_rccl_request_on_one_gpu():
     env = dict(os.environ, PZ_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), str(REPO / "bench.py"), "--gpus", "2", "--steps", "32",
-           "--warmup", "4", "--burn-in", "64", "--min-time", "0.05", "--no-cpu"]
+           "--warmup", "4", "--burn-in", "64", "--full", "--no-cpu"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(REPO))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["ranks"] == 2 and out["rccl_ranks"] == 0 and out["dist_backend"] == "gloo"
     assert "share one GPU" in out["dist_note"]
-    assert all(p["parity_bit_exact"] is None for p in out["per_rank"])  # --no-cpu: nothing was replayed
+    assert all(p["parity_bit_exact"] is None for p in out["per_rank"])  # --full --no-cpu: nothing was replayed
     assert out["roofline"]["parity_first_last_rank_bit_exact"] is None and out["roofline"]["parity_ranks_checked"] == 0
     assert out["config"]["rccl_ranks"] == 0 and "share one GPU" in out["config"]["dist_note"]
 
 
 def test_the_default_bench_line_is_flat_below_8_kb_and_carries_every_baseline_config(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the driver's own command.  Its record keeps the scalar members
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's command with everything beside the headline
+    (what a plain run leaves out: the test below).  Its record keeps the scalar members
     of `config` / `roofline` / `cpu_baseline` and drops nested objects, and its stdout tail is 8 KB: so the line must be
     flat, short, and carry one scalar per figure the documents quote for a BASELINE config -- measured on the
     cold action tape whatever --steps is, with the launch-floor twin of the diagnostics library and the two-chain
     measurement beside the headline, every oracle replay of the run bit-exact, and the verbose blocks in the side file."""
     side = tmp_path / "configs.json"
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2",
-           "--configs-out", str(side)]
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds",
+           "2", "--configs-out", str(side)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(REPO))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -192,6 +193,7 @@ def test_the_default_bench_line_is_flat_below_8_kb_and_carries_every_baseline_co
         assert all(not isinstance(v, str) or len(v) <= 128 for v in out[block].values()), block  # (the record cuts strings at 128)
     cfg, roof, cpu = out["config"], out["roofline"], out["cpu_baseline"]
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5 and out["unit"] == "env-steps/s"
+    assert out["timed_steps"] == 20 and np.isclose(out["ms_per_step"], out["timed_seconds"] * 1e3 / 20, rtol=1e-9)
     assert out["dtype"] == "int32" and out["scaling"] == "weak" and out["vs_baseline"] is None and out["higher_is_better"] is True
     assert np.isclose(out["value"], 65536 / (out["ms_per_step"] * 1e-3), rtol=1e-6)
     assert cfg["action_tape"] == "cold" and cfg["action_tape_bytes"] > 1 << 30 and cfg["num_envs_per_gpu"] == 65536
@@ -220,3 +222,56 @@ def test_the_default_bench_line_is_flat_below_8_kb_and_carries_every_baseline_co
     verbose = json.loads(side.read_text())
     assert {"configs", "per_rank", "regimes", "launch_floor", "other_action_tape", "traffic_status"} <= set(verbose)
     assert verbose["configs"]["cfg3"]["parity_bit_exact"] is True and out["configs_file"] == str(side)
+
+
+def test_the_plain_bench_line_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: exactly K timed launches and the
+    headline's figures only; DIR gets what the last launch left for its caller and the state it stepped, in float32 /
+    float64, the same arrays from a second run, and that state is the CPU oracle's after the same launches."""
+    from oracle import pz_oracle as po
+
+    steps, warmup, burn = 300, 7, 512
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--burn-in", str(burn), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(REPO))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and len(lines[0]) < 8000
+        out = json.loads(lines[0])
+        assert out["steps"] == out["timed_steps"] == steps and out["warmup"] == warmup and out["replays"] == 1
+        assert np.isclose(out["ms_per_step"], out["timed_seconds"] * 1e3 / steps, rtol=1e-9)
+        assert np.isclose(out["value"], 65536 / (out["ms_per_step"] * 1e-3), rtol=1e-6)
+        assert out["metric"] == "env-steps/sec (random policy, 65 536 envs per GPU)" and out["unit"] == "env-steps/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "int32" and out["config"]["action_tape"] == "cold"
+        roof = out["roofline"]
+        assert "cpu_baseline" not in out and "configs_file" not in out
+        assert not [key for key in roof if key.startswith(("floor_", "cfg", "hot_tape", "rollout", "traffic", "two_"))]
+        assert roof["parity_ranks_checked"] == 0 and 0 < roof["frac"] < 1.0
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"obs_player_1", "obs_player_2", "reward_player_1", "reward_player_2", "terminated", "state"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert a["obs_player_1"].shape == (65536, 35) and a["reward_player_2"].shape == (65536,) and a["state"].shape == (65536, 44)
+    # burn-in, warm-up (slices 0..W-1), the graph's untimed upload and the timed replay (slices W..W+K-1 both times)
+    lanes = 1024
+    po.build()
+    chk = po.OracleEnv(lanes, po.make_config(winning_score=15, serve="winner", seed=0, env_id_base=0), nthreads=4)
+    chk.reset()
+    chk.rollout_random(2, 0, burn)
+    chk.rollout_random(1, 0, warmup)
+    chk.rollout_random(1, warmup, steps)
+    chk.rollout_random(1, warmup, steps - 1)
+    robs, rrew, rterm = chk.step(*po.random_actions(lanes, 0, 1, warmup + steps - 1))  # the last timed launch
+    assert np.array_equal(a["state"][:lanes].T.astype(np.int64), chk.state.astype(np.int64))
+    # ... and what that launch handed its caller, read from the right buffers after it
+    assert np.array_equal(a["obs_player_1"][:lanes], robs[0].astype(np.float32))
+    assert np.array_equal(a["obs_player_2"][:lanes], robs[1].astype(np.float32))
+    assert np.array_equal(a["reward_player_1"][:lanes], rrew[0].astype(np.float32))
+    assert np.array_equal(a["reward_player_2"][:lanes], rrew[1].astype(np.float32))
+    assert np.array_equal(a["terminated"][:lanes], rterm.astype(np.float32))
+    assert np.abs(a["obs_player_1"]).sum() > 0 and a["terminated"].max() <= 1

@@ -1,8 +1,9 @@
-"""Live check of the oracle against the UNMODIFIED reference, in the build container only.
+"""The oracle against the UNMODIFIED reference on runs of their own: seeds, configurations and planted states that the
+fixtures of tests/test_oracle_golden.py do not hold.
 
-The reference checkout (/root/reference) does not exist on the GPU box; there this module is skipped and the
-committed fixtures (tests/golden/, produced by the same harness) carry the parity pin.  Here it re-runs the
-capture harness on fresh seeds, so the pin does not rest on the committed files alone.
+The reference's side of every run is stored under tests/golden/live_*.npz (recorded by oracle/ref_capture.py, whose
+``write_live_fixtures`` re-runs the capture harness on the same seeds where the reference checkout is present), so
+these tests need nothing outside the repository.
 """
 import json
 
@@ -11,27 +12,21 @@ import pytest
 
 from oracle import ref_capture as rc
 
-pytestmark = pytest.mark.skipif(not rc.reference_available(), reason="reference checkout not mounted")
+GOLDEN = rc.GOLDEN
+LIVE = rc.LIVE_RUNS
 
-TABLE = [0.0, -0.01, 0.0, 0.01, 0.0, 0.01, 0.0, -0.01]
-LIVE = [
-    ("human_human", dict(winning_score=5, serve="winner"), None),
-    ("p1_computer_random_serve", dict(winning_score=3, serve="random", is_player1_computer=True), None),
-    ("both_computer_alternate", dict(winning_score=2, serve="alternate", is_player1_computer=True,
-                                     is_player2_computer=True), None),
-    ("wrapper_stack", dict(winning_score=2, is_player2_computer=True),
-     dict(stack=[["SimplifyAction", {}], ["RecordEpisodeStatistics", {}],
-                 ["RewardByBallPosition", dict(additional_reward=TABLE)],
-                 ["RewardInNormalState", dict(reward=0.03125)], ["NormalizeObservation", {}]])),
-]
+
+def _load(name):
+    return dict(np.load(GOLDEN / f"{name}.npz"))
 
 
 @pytest.mark.parametrize("name,kw,wr", LIVE)
 def test_oracle_tracks_live_reference(oracle, name, kw, wr):
     lanes, steps, seed, aseed, base = 6, 2500, 424242, 31, 99
-    d = rc.capture(name, lanes, steps, seed=seed, action_seed=aseed, env_id_base=base, env_kwargs=kw,
-                   wrappers=wr, full=True)
+    d = _load(f"live_{name}")
     meta = json.loads(bytes(d["meta"]).decode())
+    assert (meta["lanes"], meta["steps"], meta["seed"], meta["action_seed"], meta["env_id_base"]) == (lanes, steps, seed,
+                                                                                                       aseed, base)
     opt = rc.fused_options(wr)
     cfg = oracle.make_config(winning_score=kw.get("winning_score", 15), serve=kw.get("serve", "winner"),
                              is_player1_computer=kw.get("is_player1_computer", False),
@@ -63,16 +58,16 @@ def test_oracle_tracks_live_reference(oracle, name, kw, wr):
     assert meta["episodes"] == int(d["term"].sum()) and meta["episodes"] > 0
 
 
-@pytest.mark.parametrize("kw", [dict(winning_score=4), dict(winning_score=2, is_player1_computer=True, is_player2_computer=True),
-                                dict(winning_score=3, is_player2_computer=True, serve="random"),
-                                dict(winning_score=3, is_player1_computer=True, serve="alternate")])
+@pytest.mark.parametrize("kw", rc.LIVE_PLANTED)
 def test_oracle_tracks_live_reference_from_planted_states(oracle, kw):
-    """Fresh planted states on every configuration (the committed fixtures hold one draw of them): every attribute of
-    players / ball / scores at random over its valid range, plus the fast-ball corners, stepped by the live reference."""
-    for d in (rc.capture_planted_random("live", 1500, seed=31337, action_seed=5, env_id_base=7700, env_kwargs=kw,
-                                        frames=10, plant_seed=2024),
-              rc.capture_planted("live", seed=31338, action_seed=6, env_id_base=8800, env_kwargs=kw, frames=12)):
+    """Planted states of their own on every configuration (tests/test_gpu_packed.py's fixtures hold another draw of
+    them): every attribute of players / ball / scores at random over its valid range, plus the fast-ball corners,
+    stepped by the reference."""
+    stored = _load(f"live_planted_{rc.LIVE_PLANTED.index(kw)}")
+    for kind in ("random", "fast"):
+        d = {key[len(kind) + 1:]: v for key, v in stored.items() if key.startswith(kind + "_")}
         meta = json.loads(bytes(d["meta"]).decode())
+        assert {k: meta["env_kwargs"][k] for k in kw} == kw and meta["frames"] == (10 if kind == "random" else 12)
         env = oracle.OracleEnv(meta["lanes"], oracle.make_config(
             winning_score=kw.get("winning_score", 15), serve=kw.get("serve", "winner"),
             is_player1_computer=kw.get("is_player1_computer", False),
@@ -85,42 +80,19 @@ def test_oracle_tracks_live_reference_from_planted_states(oracle, kw):
 
 
 def test_draw_list_tracks_live_reference_on_planted_states():
-    """render() of the live reference on random planted states (every pose / mirroring / score digit / hyper ball, balls
+    """render() of the reference on random planted states (every pose / mirroring / score digit / hyper ball, balls
     partly or wholly off screen): the oracle's draw list equals the recorded blits (punch effect aside)."""
     from oracle import render_oracle as ro
 
-    files = ro.sprite_files()
-    sizes = None
-    rng = np.random.default_rng(77)
+    d = _load("live_draw_lists")
+    count = json.loads(bytes(d["meta"]).decode())["count"]
+    assert count == rc.LIVE_DRAW_LISTS == 400 and d["sizes"].shape == (ro.SPRITE_COUNT, 2)
+    sizes = [tuple(int(v) for v in wh) for wh in d["sizes"]]
     checked = 0
-    for i in range(400):
-        env, raw, shim = rc.make_reference_env(5, 300 + i, None, render_mode="rgb_array", winning_score=15)
-        env.reset()
-        for pl in (raw.physics.player1, raw.physics.player2):
-            pl.state = int(rng.integers(0, 5))
-            pl.frame_number = int(rng.integers(0, 5 if pl.state < 3 else (2 if pl.state == 3 else 1)))
-            pl.diving_direction = int(rng.integers(-1, 2))
-            pl.y = int(rng.integers(108, 245))
-        b = raw.physics.ball
-        b.x, b.y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
-        b.previous_x, b.previous_y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
-        b.previous_previous_x, b.previous_previous_y = int(rng.integers(20, 433)), int(rng.integers(-120, 253))
-        b.is_power_hit = bool(rng.integers(0, 2))
-        b.fine_rotation = int(rng.integers(0, 51))
-        b.rotation = b.fine_rotation // 10
-        raw.scores = [int(rng.integers(0, 16)), int(rng.integers(0, 16))]
-        raw.render()
-        blits = raw.screen.blits[rc.BACKGROUND_BLITS:]
-        if sizes is None:
-            sizes = [(0, 0)] * ro.SPRITE_COUNT
-            import struct
-            for k, f in enumerate(files):
-                with open(rc.REFERENCE_ROOT / "pikazoo" / "env" / "img" / f, "rb") as fh:
-                    head = fh.read(24)
-                sizes[k] = struct.unpack(">II", head[16:24])
-        want = [(files.index(f), int(flip), x, y, w, h) for (f, flip, scaled), x, y, w, h in blits if f != "ball_punch.png"]
-        sc = rc.extract_scenery(raw)
-        got = ro.draw_list(rc.extract_state(raw, shim), sizes, sc)
+    for i in range(count):
+        lo, hi = int(d["offsets"][i]), int(d["offsets"][i + 1])
+        want = [tuple(int(v) for v in row) for row in d["blits"][lo:hi]]
+        got = ro.draw_list(d["states"][i], sizes, d["scenery"][i])
         assert got == want, i
         checked += len(got)
     assert checked > 400 * 45

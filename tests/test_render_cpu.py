@@ -1,5 +1,6 @@
 """CPU tests of the renderer's host side: the PNG reader, the background composition and the numpy frame oracle
 (no GPU needed).  The frame itself (HIP vs oracle) is tested in tests/test_gpu_render.py."""
+import json
 import struct
 import zlib
 from pathlib import Path
@@ -7,16 +8,18 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-REFERENCE_IMG = Path("/root/reference/pikazoo/env/img")  # only in the build container; never on the GPU box
+GOLDEN = Path(__file__).resolve().parent / "golden"
 
 
-def _write_png(path, img, filter_type):
-    """A minimal 8-bit RGBA PNG writer using ONE filter type for every scanline (test fixture generator)."""
+def _write_png(path, img, filter_type, idat_parts=(1,)):
+    """A minimal 8-bit RGBA PNG writer (test fixture generator): `filter_type` is ONE filter type for every scanline or
+    one per scanline; the zlib stream is split over IDAT chunks in the proportions `idat_parts`."""
     h, w, _ = img.shape
+    row_filters = [filter_type] * h if np.isscalar(filter_type) else [int(f) for f in filter_type]
     bpp, stride = 4, w * 4
     raw = bytearray()
     prev = np.zeros(stride, np.int32)
-    for y in range(h):
+    for y, filter_type in enumerate(row_filters):
         cur = img[y].reshape(-1).astype(np.int32)
         left = np.concatenate([np.zeros(bpp, np.int32), cur[:-bpp]])
         upleft = np.concatenate([np.zeros(bpp, np.int32), prev[:-bpp]])
@@ -39,8 +42,11 @@ def _write_png(path, img, filter_type):
     def chunk(kind, body):
         return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body))
 
-    data = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0))
-            + chunk(b"IDAT", zlib.compress(bytes(raw))) + chunk(b"IEND", b""))
+    stream = zlib.compress(bytes(raw))
+    cuts = np.rint(np.cumsum(idat_parts) / np.sum(idat_parts) * len(stream)).astype(int)
+    idat = b"".join(chunk(b"IDAT", stream[lo:hi]) for lo, hi in zip([0, *cuts[:-1]], cuts))
+    data = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)) + idat
+            + chunk(b"IEND", b""))
     Path(path).write_bytes(data)
 
 
@@ -54,19 +60,36 @@ def test_png_reader_round_trip_every_filter(filter_type, tmp_path):
     assert np.array_equal(read_png_rgba(tmp_path / "t.png"), img)
 
 
-def test_png_reader_matches_pillow_on_the_reference_assets():
-    """The product reads the reference's own PNG files at run time; in the build container (reference checkout and
-    Pillow present) every asset it uses must decode to what Pillow decodes."""
+def test_png_reader_matches_pillow_on_the_reference_assets(tmp_path):
+    """The product reads the reference's own PNG files at run time: every asset it uses must decode to what Pillow
+    decodes.  The assets themselves stay out of this repository; tests/golden/reference_png_layout.npz records how each
+    is laid out (IHDR, the filter type of every scanline, the split of its IDAT chunks: oracle/ref_capture.py), and a
+    PNG of exactly that layout, with seeded pixels, goes through both decoders."""
     PIL = pytest.importorskip("PIL.Image")
-    if not REFERENCE_IMG.is_dir():
-        pytest.skip("reference assets not present (GPU box)")
     from pikazoo_amd.render import BACKGROUND_FILES, BACKGROUND_SHAPES, SPRITE_FILES, SPRITE_SHAPES, read_png_rgba
 
+    lay = dict(np.load(GOLDEN / "reference_png_layout.npz"))
+    names = json.loads(bytes(lay["meta"]).decode())["names"]
+    layout = {}
+    for k, name in enumerate(names):
+        w, h, depth, color, comp, filt, interlace = (int(v) for v in lay["ihdr"][k])
+        assert (depth, color, comp, filt, interlace) == (8, 6, 0, 0, 0), name
+        rows = lay["filters"][lay["filter_offsets"][k]:lay["filter_offsets"][k + 1]]
+        parts = lay["idat_sizes"][lay["idat_offsets"][k]:lay["idat_offsets"][k + 1]]
+        assert len(rows) == h and len(parts) >= 1, name
+        layout[name] = (w, h, rows, parts)
+    assert set(layout) >= set(SPRITE_FILES) | set(BACKGROUND_FILES)
+    rng = np.random.default_rng(2024)
     for name, shape in list(zip(SPRITE_FILES, SPRITE_SHAPES)) + [(f, BACKGROUND_SHAPES[f]) for f in BACKGROUND_FILES]:
-        mine = read_png_rgba(REFERENCE_IMG / name)
-        ref = np.asarray(PIL.open(REFERENCE_IMG / name).convert("RGBA"))
+        w, h, rows, parts = layout[name]
+        img = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+        img[..., 3] = np.where(rng.random((h, w)) < 0.5, img[..., 3], rng.choice([0, 255], (h, w)))
+        path = tmp_path / name
+        _write_png(path, img, rows, parts)
+        mine = read_png_rgba(path)
+        ref = np.asarray(PIL.open(path).convert("RGBA"))
         assert mine.shape == (shape[1], shape[0], 4), name
-        assert np.array_equal(mine, ref), name
+        assert np.array_equal(mine, ref) and np.array_equal(mine, img), name
 
 
 def test_blend_rule_and_background_composition():

@@ -3,12 +3,12 @@
 # gpurun_out/TAG/, copy what is to be judged into profiles/).  Every step runs under its own `timeout -k 10`, and a step
 # that fails ends the script: no GPU step is started behind a failed one.
 #
-#   check   GPU test suite, __graft_entry__.smoke(), the default bench line (+ its --configs-out file)
+#   check   GPU test suite, __graft_entry__.smoke(), the --full bench line (+ its --configs-out file)
 #   tables  config 3 in the three flight-table modes (both / power-hit table only / none), interleaved in one process on one
 #           library, cold and hot action tape; then DESIGN 4.2's early stores re-measured on the round's kernels
-#   bench   the default bench line and the --extra line only
+#   bench   the --full bench line and the --full --extra line only
 #   driver  the bench line exactly as the driver runs it (--steps 20 --warmup 5)
-#   variants  the bench line's other workloads and launch modes, headline only (--no-configs): config 3, config 5, packed,
+#   variants  the bench line's other workloads and launch modes, headline only (--full --no-configs): config 3, config 5, packed,
 #           int16 rows, hot tape, direct C-ABI launches, env.step(), two ranks on one device over gloo -- each must print
 #           a line with its in-run oracle parity true
 #   edge    config 3's early stores: A/B of the LDS hand-shake against round 4's unordered form and against no
@@ -52,12 +52,12 @@ check)
     tail -n 4 "$O/gputest.log"
     step 300 smoke.log python3 -c "import __graft_entry__ as g; g.smoke()"
     tail -n 1 "$O/smoke.log"
-    timeout -k 10 600 python3 bench.py --configs-out "$O/bench_configs.json" > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo "bench failed"; tail "$O/bench_default.err"; exit 1; }
+    timeout -k 10 600 python3 bench.py --full --configs-out "$O/bench_configs.json" > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo "bench failed"; tail "$O/bench_default.err"; exit 1; }
     bench_summary "$O/bench_default.json"
     ;;
 bench)
-    timeout -k 10 600 python3 bench.py --configs-out "$O/bench_configs.json" > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo "bench failed"; tail "$O/bench_default.err"; exit 1; }
-    timeout -k 10 900 python3 bench.py --extra --configs-out "$O/bench_extra_configs.json" > "$O/bench_default_extra.json" 2> "$O/bench_extra.err" || { echo "bench --extra failed"; tail "$O/bench_extra.err"; exit 1; }
+    timeout -k 10 600 python3 bench.py --full --configs-out "$O/bench_configs.json" > "$O/bench_default.json" 2> "$O/bench_default.err" || { echo "bench failed"; tail "$O/bench_default.err"; exit 1; }
+    timeout -k 10 900 python3 bench.py --full --extra --configs-out "$O/bench_extra_configs.json" > "$O/bench_default_extra.json" 2> "$O/bench_extra.err" || { echo "bench --extra failed"; tail "$O/bench_extra.err"; exit 1; }
     bench_summary "$O/bench_default.json" "$O/bench_default_extra.json"
     ;;
 driver)
@@ -68,10 +68,10 @@ variants)
     for v in "--p2-computer" "--wrappers" "--state-format packed" "--int16-obs" "--action-tape hot --steps 20 --warmup 5" \
              "--launch cabi --steps 500" "--launch api --steps 500" "--p2-computer --no-flight-tables" "--p1-computer"; do
         name=$(echo "$v" | tr -c 'a-z0-9\n' '_')
-        step 300 "bench$name.json" python3 bench.py --no-configs --min-time 0.1 --cpu-seconds 2 $v
+        step 300 "bench$name.json" python3 bench.py --full --no-configs --cpu-seconds 2 $v
     done
     step 400 quickstart.log python3 examples/quickstart.py
-    PZ_BENCH_ONE_DEVICE=1 timeout -k 10 400 python3 bench.py --gpus 2 --no-configs --min-time 0.1 --dist-backend gloo --p2-computer > "$O/bench_two_ranks_cfg3.json" 2> "$O/bench_two_ranks_cfg3.err" || { echo "two ranks failed"; tail "$O/bench_two_ranks_cfg3.err"; exit 1; }
+    PZ_BENCH_ONE_DEVICE=1 timeout -k 10 400 python3 bench.py --gpus 2 --full --no-configs --dist-backend gloo --p2-computer > "$O/bench_two_ranks_cfg3.json" 2> "$O/bench_two_ranks_cfg3.err" || { echo "two ranks failed"; tail "$O/bench_two_ranks_cfg3.err"; exit 1; }
     python3 - "$O"/bench*.json <<'PY'
 import json, sys
 bad = 0

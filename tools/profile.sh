@@ -59,7 +59,7 @@ pmc_set() {  # prefix, bench args...
 
 for s in $SECTIONS; do
     case $s in
-    kt) run kt --kernel-trace --stats -- $PY bench.py --no-cpu || exit 1 ;;
+    kt) run kt --kernel-trace --stats -- $PY bench.py --full --no-cpu || exit 1 ;;
     pmc_hh) pmc_set hh --no-cpu --no-configs --steps 40 --warmup 10 --burn-in 512 --launch cabi || exit 1 ;;
     pmc_cfg3) pmc_set cfg3 --no-cpu --no-configs --p2-computer --steps 40 --warmup 10 --burn-in 512 --launch cabi || exit 1 ;;
     pmc_cfg3q) pmc_set cfg3q --no-cpu --no-configs --p2-computer --flight-tables power_hit --steps 40 --warmup 10 --burn-in 512 --launch cabi || exit 1 ;;
