@@ -2229,6 +2229,14 @@ constexpr bool dev_keep(int family, int mode, bool ai1, bool ai2, bool packed, b
            (!obs16 || ((m >> 5) & 1u)) && form;
 }
 #define PZ_KEEP(...) pz::dev_keep(__VA_ARGS__)
+// instantiations no launch of the product can reach are not built (a branch to one returns PZ_E_CONFIG, as a dev_keep
+// exclusion does): human vs human takes the pair rollout only on int16 rows (kHhPairRollout == 1), and a packed
+// human-vs-human pz_step always takes step_pair_kernel -- but for the diagnostic builds without it (diag::kNoPairKernel)
+constexpr bool rollout_pair_reachable(bool ai1, bool ai2, bool obs16) { return ai1 || ai2 || obs16 || kHhPairRollout == 2; }
+constexpr bool single_reachable(int mode, bool ai1, bool ai2, bool packed)
+{
+    return ai1 || ai2 || !packed || mode != kActions || diag::kNoPairKernel;
+}
 
 // one step_kernel instantiation per player configuration; the trajectory modes also per observation row format
 // (OBS16, compile-time there: see TrajOut::flush)
@@ -2248,7 +2256,7 @@ static int launch_step_players(const StepArgs& a, hipStream_t stream)
 #define PZ_PLAIN_HERE(A1, A2) (kHasPlain && !(kHhRolloutGeneric && MODE == kRollout && !(A1) && !(A2)))
 #define PZ_LAUNCH_SINGLE_AS(A1, A2, PLAIN)                                                                                \
     do {                                                                                                                  \
-        if constexpr (PZ_KEEP(kDevSingle, MODE, A1, A2, PACKED, OBS16, PLAIN))                                             \
+        if constexpr (PZ_KEEP(kDevSingle, MODE, A1, A2, PACKED, OBS16, PLAIN) && single_reachable(MODE, A1, A2, PACKED))   \
             hipLaunchKernelGGL((step_kernel<A1, A2, MODE, SPARSE, SCOUT, PACKED, OBS16, PLAIN>), grid, block, 0, stream,   \
                                PZ_HOT_ARGS(a), a);                                                                        \
         else                                                                                                              \
@@ -2342,7 +2350,7 @@ static int launch_step(const StepArgs& a, hipStream_t stream)
         const bool packed = is_packed(a.cfg), obs16 = a.cfg.normalize_obs == 2, plain = is_plain(a);
 #define PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, PK, O16, PLAIN)                                                                 \
     do {                                                                                                                  \
-        if constexpr (PZ_KEEP(kDevRolloutPair, MODE, A1, A2, PK, O16, PLAIN))                                              \
+        if constexpr (PZ_KEEP(kDevRolloutPair, MODE, A1, A2, PK, O16, PLAIN) && rollout_pair_reachable(A1, A2, O16))        \
             hipLaunchKernelGGL((rollout_pair_kernel<A1, A2, MODE, PK, O16, PLAIN>), grid, block, 0, stream,                \
                                PZ_HOT_ARGS(a), a);                                                                        \
         else                                                                                                              \

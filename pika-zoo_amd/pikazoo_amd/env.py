@@ -81,18 +81,20 @@ def flight_tables(device: torch.device, landing: bool = True, power_hit: bool = 
     """``(PzFlightTables, landing, power_hit)`` of `device`; each table is built on first use and kept per device
     (``landing``: 927 MB, ``power_hit``: 82 MB; a table that was not asked for is NULL in the struct)."""
     key = device.index
-    have = _FLIGHT_TABLES.setdefault(key, {})
+    have = _FLIGHT_TABLES.get(key, {})
     lib = _native.load()
     want = [w for w, on in (("landing", landing), ("power_hit", power_hit)) if on and w not in have]
     if want:
+        # built into locals and published only once built: a failed allocation or build leaves the cache as it was,
+        # never holding an unbuilt table that a later env's computer player would decide on
         with torch.cuda.device(device):
-            for which in want:
-                have[which] = torch.empty(lib.pz_flight_table_bytes(0 if which == "landing" else 1), dtype=torch.uint8,
-                                          device=device)
-            _native.check(lib.pz_build_flight_tables(have["landing"].data_ptr() if "landing" in want else None,
-                                                     have["power_hit"].data_ptr() if "power_hit" in want else None,
+            built = {which: torch.empty(lib.pz_flight_table_bytes(0 if which == "landing" else 1), dtype=torch.uint8,
+                                        device=device) for which in want}
+            _native.check(lib.pz_build_flight_tables(built["landing"].data_ptr() if "landing" in built else None,
+                                                     built["power_hit"].data_ptr() if "power_hit" in built else None,
                                                      _raw_stream(key)), "pz_build_flight_tables")
             torch.cuda.current_stream(device).synchronize()  # envs on other streams may use them right away
+        have = _FLIGHT_TABLES[key] = {**have, **built}
     t_landing = have["landing"] if landing else None
     t_hit = have["power_hit"] if power_hit else None
     return _native.PzFlightTables(_ptr(t_landing), _ptr(t_hit)), t_landing, t_hit

@@ -681,3 +681,35 @@ def test_no_scratch_and_bounded_scalar_spills_in_the_step_kernels(built_lib, tmp
     for name, most in bounds.items():
         assert name in step, f"{name} is not in the library"
         assert step[name][".sgpr_spill_count"] <= most, f"{name}: {step[name]['.sgpr_spill_count']} SGPR spills (> {most})"
+
+
+def test_kernel_matrix_names_exactly_the_step_kernels_in_the_library(built_lib):
+    """tests/kernel_matrix.py holds one launch configuration per step-kernel instantiation the C ABI can dispatch, and
+    tests/test_gpu_kernel_matrix.py runs each against the oracle and checks the kernel it dispatched by name.  That
+    set equals the step_kernel / step_pair_kernel / rollout_pair_kernel instantiations in the gfx950 code object: an
+    instantiation added without a row, a row naming a kernel the library does not hold, and an instantiation left in
+    the library that no launch can reach all fail here."""
+    sys.path.insert(0, str(REPO / "tools"))
+    import kernel_digest
+    import kernel_matrix
+
+    if not kernel_digest.available():
+        pytest.skip("llvm-objdump not available")
+    shipped = {name.replace("pz::", "", 1) for name in kernel_digest.kernels(built_lib)}
+    shipped = {name for name in shipped if name.startswith(kernel_matrix.FAMILIES)}
+    assert len(shipped) > 100, "the scan did not see the step kernels"
+    unlisted = sorted(shipped - kernel_matrix.KERNELS)
+    missing = sorted(kernel_matrix.KERNELS - shipped)
+    assert not unlisted, f"instantiations without a matrix row (unreachable, or the dispatch changed): {unlisted}"
+    assert not missing, f"matrix rows naming kernels the library does not hold: {missing}"
+    # every row's kernel is the one the restated dispatch picks for its configuration; a computer player's kernel on the
+    # flight tables runs under both table modes
+    for row in kernel_matrix.ROWS:
+        assert kernel_matrix.dispatch(row.entry, row.k, row.n, row.packed, row.obs16, row.plain, row.tables, row.p1,
+                                      row.p2) == row.kernel, row.id
+        assert row.above == (row.n >= kernel_matrix.SWITCH) and row.n % 8 == 0 and row.stride > row.n
+    ids = [row.id for row in kernel_matrix.ROWS]
+    assert len(ids) == len(set(ids))
+    for row in kernel_matrix.ROWS:
+        if row.tables == "both":
+            assert f"{row.kernel} [power_hit]" in ids

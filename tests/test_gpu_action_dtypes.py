@@ -205,3 +205,55 @@ def test_flight_table_modes_cost_what_the_readme_says():
     assert make(64, seed=1, is_player2_computer=True).flight_tables == "both" and make(64, seed=1).flight_tables == "none"
     with pytest.raises(ValueError):
         make(64, flight_tables="landing")
+
+
+def test_a_failed_flight_table_build_caches_nothing(monkeypatch, oracle):
+    """flight_tables() publishes a device's tables only once they are built: an allocation or a build that fails
+    raises and leaves the cache as it was -- a cached unbuilt (torch.empty) table would have every later env's computer
+    player decide on uninitialised memory without an error.  With the fault gone, a computer-player env builds the
+    tables and runs bit-exact against the oracle."""
+    from pikazoo_amd import _native
+    from pikazoo_amd import env as E
+
+    monkeypatch.setattr(E, "_FLIGHT_TABLES", {})  # (the other tests keep theirs)
+    dev = torch.device("cuda:0")
+    lib = _native.load()
+    real_build, real_empty = lib.pz_build_flight_tables, torch.empty
+    builds, allocations = [], []
+
+    def build_fails_once(*args):
+        builds.append(args)
+        return -3 if len(builds) == 1 else real_build(*args)  # (PZ_E_CONFIG)
+
+    monkeypatch.setattr(lib, "pz_build_flight_tables", build_fails_once)
+    with pytest.raises(_native.PikazooNativeError, match="pz_build_flight_tables"):
+        E.flight_tables(dev)
+    assert len(builds) == 1 and E._FLIGHT_TABLES.get(0, {}) == {}
+
+    def second_allocation_fails(*args, **kw):
+        allocations.append(args)
+        if len(allocations) == 2:
+            raise torch.cuda.OutOfMemoryError("injected: the second table does not fit")
+        return real_empty(*args, **kw)
+
+    monkeypatch.setattr(torch, "empty", second_allocation_fails)
+    with pytest.raises(torch.cuda.OutOfMemoryError, match="injected"):
+        E.flight_tables(dev)
+    monkeypatch.setattr(torch, "empty", real_empty)
+    assert len(allocations) == 2 and len(builds) == 1 and E._FLIGHT_TABLES.get(0, {}) == {}
+
+    n, frames = 1024, 300
+    kw = dict(winning_score=2, serve="random", is_player1_computer=True, is_player2_computer=True)
+    env = make(n, seed=23, env_id_base=5, flight_tables=True, **kw)
+    assert len(builds) == 2 and set(E._FLIGHT_TABLES[0]) == {"landing", "power_hit"}
+    ref = oracle_env(oracle, n, 23, 5, **kw)
+    obs, _ = env.reset()
+    ref.reset()
+    for t in range(frames):
+        acts = env.random_actions(31, t)
+        obs, rew, term, _, _ = env.step(acts)
+        ref.step(cpu(acts["player_1"]), cpu(acts["player_2"]))
+        if t % 50 == 49:
+            assert np.array_equal(cpu(env.state), ref.state), t
+    assert np.array_equal(cpu(obs["player_1"]), ref.obs[0]) and np.array_equal(cpu(rew["player_2"]), ref.rew[1])
+    assert np.array_equal(cpu(term["player_1"]).astype(np.uint8), ref.term)
