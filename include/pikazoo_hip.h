@@ -17,8 +17,8 @@
  *  - state is int32[PZ_STATE_WORDS][stride], field-major (structure of arrays): lane i
  *    (one independent game) owns column i; `n` lanes are live, stride >= n -- or, with
  *    cfg->packed_state, the bit-packed format below (36 bytes per game instead of 176);
- *  - observations are int32[n][35] row-major per agent (pikazoo_env.py:576-624), or float32 / int16 rows as
- *    cfg->normalize_obs names;
+ *  - observations are int32[n][35] row-major per agent (pikazoo_env.py:576-624), or float32 / int16 / float16 /
+ *    bfloat16 rows as cfg->normalize_obs names (enum pz_obs_format);
  *  - actions are int32 / int64 / uint8 / int16 vectors as cfg->action_format names (what the caller's policy
  *    produced: nothing is cast on the way in); an action outside the range is counted into cfg->action_faults on its
  *    FULL value (the reference raises IndexError at pikazoo_env.py:182), see pz_config.
@@ -34,7 +34,9 @@ extern "C" {
 
 /* 10: pz_config grows to 120 bytes: action_format (int64 / uint8 / int16 action vectors straight into the launch,
  *     range-checked on the full value; pz_step / pz_step_bound take `const void *` action vectors); the landing table
- *     of pz_flight_tables is optional on its own (power_hit alone is a supported mode).
+ *     of pz_flight_tables is optional on its own (power_hit alone is a supported mode).  Later, additively (same
+ *     layout, same version): normalize_obs / pz_observe's `normalize` take the float16 and bfloat16 formats 3 - 6 of
+ *     enum pz_obs_format -- a caller that never sets them sees no difference.
  *  9: the diagnostics pz_probe_launch / pz_selftest_predictor left this library (include/pikazoo_diag.h,
  *     libpikazoo_diag.so) */
 #define PZ_ABI_VERSION 10
@@ -70,6 +72,17 @@ enum pz_serve_mode { PZ_SERVE_WINNER = 0, PZ_SERVE_ALTERNATE = 1, PZ_SERVE_RANDO
  * Categorical.sample, randint), small policies emit uint8 / int16.  The launch loads the element as it is and checks
  * the FULL value against [0, n_actions): an int64 of 2**32 + 3 or -1 is a fault, never action 3. */
 enum pz_action_format { PZ_ACT_I32 = 0, PZ_ACT_I64 = 1, PZ_ACT_U8 = 2, PZ_ACT_I16 = 3 };
+
+/* observation row format (pz_config.normalize_obs, pz_observe's `normalize`).  I32 is the reference's Box dtype;
+ * F32_NORM is NormalizeObservation (normalize_observation.py:18-35), the IEEE float32 quotient (obs - low) / (high - low).
+ * The 2-byte formats hold 70-byte rows: I16 the values of I32; F16 / BF16 those values rounded to float16 / bfloat16
+ * (round to nearest even: exact in float16 -- every value has |v| <= 432 --, bfloat16 rounds values above 256);
+ * F16_NORM / BF16_NORM the F32_NORM value rounded the same way.  A 2-byte tensor holds an EVEN number of rows
+ * (n rounded up), and the k-frame launches then need n % 8 == 0. */
+enum pz_obs_format {
+    PZ_OBS_I32 = 0, PZ_OBS_F32_NORM = 1, PZ_OBS_I16 = 2, PZ_OBS_F16 = 3, PZ_OBS_BF16 = 4, PZ_OBS_F16_NORM = 5,
+    PZ_OBS_BF16_NORM = 6
+};
 
 enum pz_error {
     PZ_OK = 0,
@@ -108,11 +121,13 @@ typedef struct pz_config {
     int32_t normal_state_mode;    /* RewardInNormalState (reward_in_normal_state.py:10-15): 0 off,
                                      1 applied before additional_reward, 2 after it */
     float   normal_state_reward;  /* its constant (reward_in_normal_state.py:8) */
-    int32_t normalize_obs;        /* observation format: 0 int32 (the reference's Box dtype); 1 NormalizeObservation
-                                     (normalize_observation.py:18-35): float32 (obs - low) / (high - low); 2 int16: the
-                                     values of format 0 in 70-byte rows -- the observation tensors are the largest
-                                     stream a step writes, this halves them.  A format-2 tensor holds an EVEN number
-                                     of rows (n rounded up); k-frame launches then need n % 8 == 0 */
+    int32_t normalize_obs;        /* observation format, enum pz_obs_format: 0 int32 (the reference's Box dtype); 1
+                                     NormalizeObservation (normalize_observation.py:18-35): float32 (obs - low) /
+                                     (high - low); 2 int16: the values of format 0 in 70-byte rows -- the observation
+                                     tensors are the largest stream a step writes, this halves them; 3 / 4 float16 /
+                                     bfloat16 of format 0's values, 5 / 6 of format 1's, in 70-byte rows too.  A
+                                     2-byte tensor (formats 2 - 6) holds an EVEN number of rows (n rounded up); k-frame
+                                     launches then need n % 8 == 0 */
     int32_t episode_stats_mode;   /* RecordEpisodeStatistics (record_episode_statistics.py:27-40): 0 off,
                                      1 sums the env's own reward, 2 the fully wrapped reward */
     uint64_t seed;                /* Philox4x32-10 key of the env RNG stream */

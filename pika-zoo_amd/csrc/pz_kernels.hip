@@ -356,51 +356,64 @@ __device__ __forceinline__ RngId make_rng_id(const pz_config& cfg, int64_t lane_
 // Row layout: player(13) | opponent(13) | ball(9).  Rows go to LDS at stride 35 words (odd,
 // so the 64 lanes of a ds_write_b32 hit 32 distinct banks twice = conflict-free), then the
 // wave copies the contiguous 64x35-word span to HBM with 16-byte lanes.
-// NORM: NormalizeObservation fused (normalize_observation.py:22,30): every entry becomes
+// F: the staged word's format (enum pz_obs_format; int16 rows stage what int32 rows do, flush_rows16 narrows them).
+// PZ_OBS_F32_NORM: NormalizeObservation fused (normalize_observation.py:22,30): every entry becomes
 // float32 (v - low) / (high - low) with the bounds of pikazoo_env.py:485-562.  The reference
 // divides in float64; for these small integers the correctly rounded float32 quotient is the
 // float32 rounding of that double, so an IEEE float division reproduces it bit for bit.
-template <bool NORM>
+// The float16 / bfloat16 formats: the float32 value of format 0 (exact) or 1, rounded to nearest even by a plain cast
+// (v_cvt_f16_f32 / v_cvt_pk_bf16_f32; never the round-toward-zero v_cvt_pkrtz_f16_f32), its 16-bit pattern
+// zero-extended into the staged dword -- the 2-byte flushes keep the low half of every staged dword.
+constexpr bool obs_norm(int f) { return f == PZ_OBS_F32_NORM || f == PZ_OBS_F16_NORM || f == PZ_OBS_BF16_NORM; }
+template <int F>
 __device__ __forceinline__ int32_t obs_word(int v, int low, int range)
 {
-    if (!NORM) return v;
-    const float f = (range == 1) ? (float)(v - low) : (float)(v - low) / (float)range;
-    return (int32_t)__float_as_uint(f);
+    if constexpr (F == PZ_OBS_I32 || F == PZ_OBS_I16) {
+        return v;
+    } else {
+        const float f = !obs_norm(F) ? (float)v : (range == 1) ? (float)(v - low) : (float)(v - low) / (float)range;
+        if constexpr (F == PZ_OBS_F32_NORM)
+            return (int32_t)__float_as_uint(f);
+        else if constexpr (F == PZ_OBS_F16 || F == PZ_OBS_F16_NORM)
+            return (int32_t)(uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+        else
+            return (int32_t)(uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+    }
 }
 
-template <bool NORM>
+template <int F>
 __device__ __forceinline__ void player_words(const Player& p, int32_t (&w)[13])
 {
-    w[0] = obs_word<NORM>(p.x, 32, 368);
-    w[1] = obs_word<NORM>(p.y, 108, 136);
-    w[2] = obs_word<NORM>(p.yv, -15, 31);
-    w[3] = obs_word<NORM>(p.dive, -1, 2);
-    w[4] = obs_word<NORM>(p.lying, -2, 5);
-    w[5] = obs_word<NORM>(p.frame, 0, 4);
-    w[6] = obs_word<NORM>(p.delay, 0, 4);
-    w[7] = obs_word<NORM>(p.state == 0, 0, 1);
-    w[8] = obs_word<NORM>(p.state == 1, 0, 1);
-    w[9] = obs_word<NORM>(p.state == 2, 0, 1);
-    w[10] = obs_word<NORM>(p.state == 3, 0, 1);
-    w[11] = obs_word<NORM>(p.state == 4, 0, 1);
-    w[12] = obs_word<NORM>(p.hitprev, 0, 1);
+    w[0] = obs_word<F>(p.x, 32, 368);
+    w[1] = obs_word<F>(p.y, 108, 136);
+    w[2] = obs_word<F>(p.yv, -15, 31);
+    w[3] = obs_word<F>(p.dive, -1, 2);
+    w[4] = obs_word<F>(p.lying, -2, 5);
+    w[5] = obs_word<F>(p.frame, 0, 4);
+    w[6] = obs_word<F>(p.delay, 0, 4);
+    w[7] = obs_word<F>(p.state == 0, 0, 1);
+    w[8] = obs_word<F>(p.state == 1, 0, 1);
+    w[9] = obs_word<F>(p.state == 2, 0, 1);
+    w[10] = obs_word<F>(p.state == 3, 0, 1);
+    w[11] = obs_word<F>(p.state == 4, 0, 1);
+    w[12] = obs_word<F>(p.hitprev, 0, 1);
 }
 
-template <bool NORM>
+template <int F>
 __device__ __forceinline__ void stage_obs_t(const Game& g, int32_t* __restrict__ s1, int32_t* __restrict__ s2, int lane)
 {
     int32_t p1[13], p2[13], bw[9];
-    player_words<NORM>(g.p1, p1);
-    player_words<NORM>(g.p2, p2);
-    bw[0] = obs_word<NORM>(g.b.x, 20, 412);
-    bw[1] = obs_word<NORM>(g.b.y, 0, 252);
-    bw[2] = obs_word<NORM>(g.b.px, 0, 432);
-    bw[3] = obs_word<NORM>(g.b.py, 0, 252);
-    bw[4] = obs_word<NORM>(g.b.ppx, 0, 432);
-    bw[5] = obs_word<NORM>(g.b.ppy, 0, 252);
-    bw[6] = obs_word<NORM>(g.b.xv, -20, 40);
-    bw[7] = obs_word<NORM>(g.b.yv, -124, 248);
-    bw[8] = obs_word<NORM>(g.b.power, 0, 1);
+    player_words<F>(g.p1, p1);
+    player_words<F>(g.p2, p2);
+    bw[0] = obs_word<F>(g.b.x, 20, 412);
+    bw[1] = obs_word<F>(g.b.y, 0, 252);
+    bw[2] = obs_word<F>(g.b.px, 0, 432);
+    bw[3] = obs_word<F>(g.b.py, 0, 252);
+    bw[4] = obs_word<F>(g.b.ppx, 0, 432);
+    bw[5] = obs_word<F>(g.b.ppy, 0, 252);
+    bw[6] = obs_word<F>(g.b.xv, -20, 40);
+    bw[7] = obs_word<F>(g.b.yv, -124, 248);
+    bw[8] = obs_word<F>(g.b.power, 0, 1);
     int32_t* r1 = s1 + lane * PZ_OBS_DIM;
     int32_t* r2 = s2 + lane * PZ_OBS_DIM;
 #pragma unroll
@@ -418,41 +431,74 @@ __device__ __forceinline__ void stage_obs_t(const Game& g, int32_t* __restrict__
 }
 
 // one agent's row: [own player | opponent | ball] (pair kernel: each wave packs its own agent's tensor)
-template <bool NORM>
+template <int F>
 __device__ __forceinline__ void stage_one_obs_t(const Player& me, const Player& opp, const Ball& b,
                                                 int32_t* __restrict__ dst, int lane)
 {
     int32_t pa[13], pb[13];
-    player_words<NORM>(me, pa);
-    player_words<NORM>(opp, pb);
+    player_words<F>(me, pa);
+    player_words<F>(opp, pb);
     int32_t* r = dst + lane * PZ_OBS_DIM;
 #pragma unroll
     for (int k = 0; k < 13; ++k) {
         r[k] = pa[k];
         r[13 + k] = pb[k];
     }
-    r[26] = obs_word<NORM>(b.x, 20, 412);
-    r[27] = obs_word<NORM>(b.y, 0, 252);
-    r[28] = obs_word<NORM>(b.px, 0, 432);
-    r[29] = obs_word<NORM>(b.py, 0, 252);
-    r[30] = obs_word<NORM>(b.ppx, 0, 432);
-    r[31] = obs_word<NORM>(b.ppy, 0, 252);
-    r[32] = obs_word<NORM>(b.xv, -20, 40);
-    r[33] = obs_word<NORM>(b.yv, -124, 248);
-    r[34] = obs_word<NORM>(b.power, 0, 1);
+    r[26] = obs_word<F>(b.x, 20, 412);
+    r[27] = obs_word<F>(b.y, 0, 252);
+    r[28] = obs_word<F>(b.px, 0, 432);
+    r[29] = obs_word<F>(b.py, 0, 252);
+    r[30] = obs_word<F>(b.ppx, 0, 432);
+    r[31] = obs_word<F>(b.ppy, 0, 252);
+    r[32] = obs_word<F>(b.xv, -20, 40);
+    r[33] = obs_word<F>(b.yv, -124, 248);
+    r[34] = obs_word<F>(b.power, 0, 1);
 }
 
+// The staging of the run-time format `fmt` (cfg.normalize_obs: wave-uniform, a config scalar).  ROWS: the formats the
+// calling kernel can meet -- the trajectory kernels compile the row width in (OBS16), so theirs carry the staging of
+// their own width only.  The single-frame kernels carry all of them: +0.9 % on the headline, +1.2 % on config 3
+// (profiles/obs_formats_ab.log); staging format 0 / 1 and narrowing the row in place instead measured +1.0 % there and
+// made the 16-bit single-frame launches a third slower.
+enum ObsRows { kRows4 = 1, kRows2 = 2, kRowsAny = 3 };  // 140-byte rows (formats 0, 1) / 70-byte rows (2 - 6) / both
+template <int ROWS = kRowsAny>
 __device__ __forceinline__ void stage_obs(const Game& g, int32_t* __restrict__ s1, int32_t* __restrict__ s2, int lane,
-                                          bool normalize)
+                                          int fmt)
 {
-    if (normalize)  // wave-uniform (a config scalar)
-        stage_obs_t<true>(g, s1, s2, lane);
+    if ((ROWS & kRows4) && fmt == PZ_OBS_F32_NORM)
+        stage_obs_t<PZ_OBS_F32_NORM>(g, s1, s2, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_F16)
+        stage_obs_t<PZ_OBS_F16>(g, s1, s2, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_BF16)
+        stage_obs_t<PZ_OBS_BF16>(g, s1, s2, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_F16_NORM)
+        stage_obs_t<PZ_OBS_F16_NORM>(g, s1, s2, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_BF16_NORM)
+        stage_obs_t<PZ_OBS_BF16_NORM>(g, s1, s2, lane);
+    else  // int32 / int16: the raw integers
+        stage_obs_t<PZ_OBS_I32>(g, s1, s2, lane);
+}
+
+template <int ROWS = kRowsAny>
+__device__ __forceinline__ void stage_one_obs(const Player& me, const Player& opp, const Ball& b,
+                                              int32_t* __restrict__ dst, int lane, int fmt)
+{
+    if ((ROWS & kRows4) && fmt == PZ_OBS_F32_NORM)
+        stage_one_obs_t<PZ_OBS_F32_NORM>(me, opp, b, dst, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_F16)
+        stage_one_obs_t<PZ_OBS_F16>(me, opp, b, dst, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_BF16)
+        stage_one_obs_t<PZ_OBS_BF16>(me, opp, b, dst, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_F16_NORM)
+        stage_one_obs_t<PZ_OBS_F16_NORM>(me, opp, b, dst, lane);
+    else if ((ROWS & kRows2) && fmt == PZ_OBS_BF16_NORM)
+        stage_one_obs_t<PZ_OBS_BF16_NORM>(me, opp, b, dst, lane);
     else
-        stage_obs_t<false>(g, s1, s2, lane);
+        stage_one_obs_t<PZ_OBS_I32>(me, opp, b, dst, lane);
 }
 
 
-// cfg.normalize_obs == 2: int16 observations.  The rows are staged as int32 like always and narrowed on the way out:
+// cfg.normalize_obs 2 - 6: 2-byte observations.  The rows are staged as dwords like always and narrowed on the way out:
 // a lane reads eight staged values (two 16-byte LDS reads) and writes them as one 16-byte piece of the wave's
 // contiguous 64 x 70-byte span -- 5 passes instead of 9, half the bytes.  `tensor_bytes` covers an EVEN number of rows
 // (the caller pads an odd batch by one row): the last value of an odd row count shares its dword with the padding.
@@ -477,11 +523,12 @@ __device__ __forceinline__ void flush_rows16(const int32_t* __restrict__ lds, co
 }
 
 // one agent's staged rows to frame `t` of its observation tensor, in the format cfg.normalize_obs names
-// (0: int32, 1: float32 bit patterns -- both 140-byte rows --, 2: int16, 70-byte rows of an even row count)
+// (0: int32, 1: float32 bit patterns -- both 140-byte rows --, 2 - 6: int16 / float16 / bfloat16 patterns, 70-byte rows
+// of an even row count)
 __device__ __forceinline__ void flush_obs(const int32_t* __restrict__ lds, void* tensor, int64_t t, int64_t n, int format,
                                           int lane)
 {
-    if (format == 2) {
+    if (format >= PZ_OBS_I16) {
         const int64_t rows = (n + 1) & ~(int64_t)1;
         flush_rows16(lds, static_cast<char*>(tensor) + t * rows * (PZ_OBS_DIM * 2), (uint32_t)(rows * (PZ_OBS_DIM * 2)), lane);
     } else {
@@ -716,7 +763,7 @@ __device__ __forceinline__ void emit_outputs(const StepArgs& a, const Game& g, c
         __builtin_amdgcn_raw_buffer_store_b32(as_float ? __float_as_uint(r.f2) : (unsigned int)r.i2, rew2, voff, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b8((unsigned char)g.e.game_ended, term, (uint32_t)i, 0, 0);
         PZ_STAMP(3);
-        stage_obs(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs == 1);
+        stage_obs(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs);
     }
     __syncthreads();
     PZ_STAMP(4);
@@ -796,7 +843,7 @@ struct TrajOut {
         __builtin_amdgcn_raw_buffer_store_b32(as_float ? __float_as_uint(r.f2) : (unsigned int)r.i2,
                                               make_rsrc(rew2, n32 * 4u), voff, 0, SMALL_AUX);
         __builtin_amdgcn_raw_buffer_store_b8((unsigned char)g.e.game_ended, make_rsrc(term, n32), ioff, 0, SMALL_AUX);
-        if (live) stage_obs(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs == 1);
+        if (live) stage_obs<OBS16 ? kRows2 : kRows4>(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs);
         // the rows are read back by this wave only: its LDS instructions execute in issue order
         wave_lds_handover<false>();
     }
@@ -951,7 +998,7 @@ __device__ __forceinline__ void scout_candidates_posted(const int32_t* __restric
 // frame of pz_step (scout_candidates, scout_landing_after_hits), kScoutPosted for the k-frame modes
 // (scout_candidates_posted).  The scout executes exactly the workgroup barriers of the main wave.
 // PACKED: the state buffer holds the packed format (pz_packed.hpp); the whole groups are written back (no scout wave).
-// OBS16 (trajectory modes only): int16 observation rows (cfg.normalize_obs == 2), compile-time there.
+// OBS16 (trajectory modes only): 2-byte observation rows (cfg.normalize_obs 2 - 6), compile-time there.
 // The compiler's occupancy target for the kernel (it steers its scheduling, not only its register budget; measured,
 // tools/ab.py, us per frame at k = 32): the rollout of the on-device policy is at its best told that one wave per
 // SIMD is all there will be (4.23 vs 4.27 with a computer player), the tape kernel -- same register count either way
@@ -1406,10 +1453,7 @@ __device__ __forceinline__ void pair_body(const StepArgs& a, const HotArgs hot, 
         if (live) {
             const Player& me = ROLE == 0 ? g.p1 : g.p2;
             const Player& opp = ROLE == 0 ? g.p2 : g.p1;
-            if (a.cfg.normalize_obs == 1)
-                stage_one_obs_t<true>(me, opp, g.b, lds_obs[ROLE], lane);
-            else
-                stage_one_obs_t<false>(me, opp, g.b, lds_obs[ROLE], lane);
+            stage_one_obs(me, opp, g.b, lds_obs[ROLE], lane, a.cfg.normalize_obs);
         }
         // A wave stages and flushes ITS OWN rows, and after the exchange barrier nobody else touches them (the partner
         // wrote its player into these rows before that barrier): the wave's LDS instructions execute in issue order,
@@ -1634,13 +1678,11 @@ __device__ __forceinline__ void rollout_pair_body(const StepArgs& a, const HotAr
                 __builtin_amdgcn_raw_buffer_store_b32(as_float ? __float_as_uint(rw.f2) : (unsigned int)rw.i2,
                                                       make_rsrc(out.rew2, n32 * 4u), out.voff, 0, traj_small_aux(AI1 || AI2));
             if (live) {
-                if (kWritesAll) {
-                    stage_obs(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs == 1);
-                } else if (a.cfg.normalize_obs == 1) {
-                    stage_one_obs_t<true>(own, other, g.b, lds_obs[ROLE], lane);
-                } else {
-                    stage_one_obs_t<false>(own, other, g.b, lds_obs[ROLE], lane);
-                }
+                constexpr int kRows = OBS16 ? kRows2 : kRows4;
+                if (kWritesAll)
+                    stage_obs<kRows>(g, lds_obs[0], lds_obs[1], lane, a.cfg.normalize_obs);
+                else
+                    stage_one_obs<kRows>(own, other, g.b, lds_obs[ROLE], lane, a.cfg.normalize_obs);
             }
             wave_lds_handover<false>();  // the rows are read back by this wave only
         }
@@ -1790,7 +1832,7 @@ __global__ __launch_bounds__(kLanes) void reset_kernel(int32_t* state, int64_t n
             if (episode_stats != nullptr)  // RecordEpisodeStatistics.reset (:23-25)
                 make_stats_io(episode_stats, true, stride, i).store(EpisodeStats{0.0, 0.0, 0});
         }
-        stage_obs(g, lds_obs[0], lds_obs[1], lane, cfg.normalize_obs == 1);
+        stage_obs(g, lds_obs[0], lds_obs[1], lane, cfg.normalize_obs);
     }
     __syncthreads();
     if (obs_p1 != nullptr) flush_obs(lds_obs[0], obs_p1, 0, n, cfg.normalize_obs, lane);
@@ -1808,7 +1850,7 @@ __global__ __launch_bounds__(kLanes) void observe_kernel(const int32_t* state, i
     if (i < n) {
         Game g;
         io.load(g);
-        stage_obs(g, lds_obs[0], lds_obs[1], lane, normalize == 1);
+        stage_obs(g, lds_obs[0], lds_obs[1], lane, normalize);
     }
     __syncthreads();
     if (obs_p1 != nullptr) flush_obs(lds_obs[0], obs_p1, 0, n, normalize, lane);
@@ -2185,11 +2227,14 @@ constexpr int64_t kTwoWaveMaxLanes = 393216;  // below: two waves per workgroup 
 //   per k frames, where the plain write-back is always right.
 
 static inline bool is_packed(const pz_config& cfg) { return (cfg.packed_state & 1) != 0; }
+// formats 2 - 6 (int16 / float16 / bfloat16): 70-byte rows, an even number per frame (the OBS16 instantiations)
+static inline bool rows16(int format) { return format >= PZ_OBS_I16; }
 // no fused wrapper, no episode statistics, raw integer rows: what the PLAIN k-frame kernels are compiled for
 static inline bool is_plain(const StepArgs& a)
 {
     return a.cfg.simplify_action == 0 && a.cfg.ballpos_reward == 0 && a.cfg.normal_state_mode == 0 &&
-           a.cfg.normalize_obs != 1 && (a.cfg.episode_stats_mode == 0 || a.episode_stats == nullptr);
+           (a.cfg.normalize_obs == PZ_OBS_I32 || a.cfg.normalize_obs == PZ_OBS_I16) &&
+           (a.cfg.episode_stats_mode == 0 || a.episode_stats == nullptr);
 }
 static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
@@ -2199,7 +2244,7 @@ static int check_common(const void* state, int64_t n, int64_t stride, const pz_c
     if (n < 0 || stride < n || stride > kMaxLanesPerLaunch) return PZ_E_SIZE;
     if (cfg->winning_score < 1 || cfg->serve_mode < 0 || cfg->serve_mode > 2 || cfg->normal_state_mode < 0 ||
         cfg->normal_state_mode > 2 || cfg->episode_stats_mode < 0 || cfg->episode_stats_mode > 2 ||
-        cfg->normalize_obs < 0 || cfg->normalize_obs > 2)
+        cfg->normalize_obs < PZ_OBS_I32 || cfg->normalize_obs > PZ_OBS_BF16_NORM)
         return PZ_E_CONFIG;
     if (cfg->packed_state != 0 && cfg->packed_state != 1) return PZ_E_CONFIG;
     if (cfg->action_format < PZ_ACT_I32 || cfg->action_format > PZ_ACT_I16) return PZ_E_CONFIG;
@@ -2290,7 +2335,7 @@ template <int MODE, bool SPARSE, bool PACKED = false, int SCOUT = kNoScout>
 static int launch_step_ai(const StepArgs& a, hipStream_t stream)
 {
     if constexpr (MODE == kRollout || MODE == kTape) {
-        if (a.cfg.normalize_obs == 2) return launch_step_players<MODE, SPARSE, SCOUT, PACKED, true>(a, stream);
+        if (rows16(a.cfg.normalize_obs)) return launch_step_players<MODE, SPARSE, SCOUT, PACKED, true>(a, stream);
     }
     return launch_step_players<MODE, SPARSE, SCOUT, PACKED, false>(a, stream);
 }
@@ -2344,10 +2389,10 @@ static int launch_step(const StepArgs& a, hipStream_t stream)
     // (interleaved A/B, us per frame at k = 32: 3.49 vs 4.34 on one wave; human vs human the single wave is at the
     // write ceiling already: 3.62 on two waves -- player 1's writing all outputs -- vs 3.63 on one, 3.76 with the
     // outputs split between the waves)
-    const bool hh_pair = !(ai1 || ai2) && (kHhPairRollout == 2 || (kHhPairRollout == 1 && a.cfg.normalize_obs == 2));
+    const bool hh_pair = !(ai1 || ai2) && (kHhPairRollout == 2 || (kHhPairRollout == 1 && rows16(a.cfg.normalize_obs)));
     if constexpr ((MODE == kRollout || MODE == kTape) && !diag::kNoRolloutPair) if (a.n < kTwoWaveMaxLanes && ((tables && (ai1 || ai2)) || hh_pair)) {
         const dim3 grid(blocks_for(a.n, kLanes)), block(2 * kLanes);
-        const bool packed = is_packed(a.cfg), obs16 = a.cfg.normalize_obs == 2, plain = is_plain(a);
+        const bool packed = is_packed(a.cfg), obs16 = rows16(a.cfg.normalize_obs), plain = is_plain(a);
 #define PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, PK, O16, PLAIN)                                                                 \
     do {                                                                                                                  \
         if constexpr (PZ_KEEP(kDevRolloutPair, MODE, A1, A2, PK, O16, PLAIN) && rollout_pair_reachable(A1, A2, O16))        \
@@ -2489,7 +2534,7 @@ int pz_observe(const int32_t* state, int64_t n, int64_t stride, int32_t normaliz
 {
     if (state == nullptr) return PZ_E_NULL;
     if (n < 0 || stride < n || stride > kMaxLanesPerLaunch) return PZ_E_SIZE;
-    if (normalize < 0 || normalize > 2) return PZ_E_CONFIG;
+    if (normalize < PZ_OBS_I32 || normalize > PZ_OBS_BF16_NORM) return PZ_E_CONFIG;
     if (misaligned16(obs_p1) || misaligned16(obs_p2) || (packed != 0 && misaligned16(state))) return PZ_E_ALIGN;
     if (n == 0) return PZ_OK;
     if (packed != 0)
@@ -2629,7 +2674,7 @@ int pz_rollout_random(int32_t* state, int64_t n, int64_t stride, const pz_config
     if (!obs_p1 || !obs_p2 || !rew_p1 || !rew_p2 || !terminated) return PZ_E_NULL;
     if (k < 1) return PZ_E_SIZE;
     // every frame's [n][35] slab must keep the 16-byte alignment of the vector stores: n * 140 % 16 == 0
-    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (cfg->normalize_obs == 2 ? 7 : 3)) != 0))
+    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (rows16(cfg->normalize_obs) ? 7 : 3)) != 0))
         return PZ_E_ALIGN;
     if (tables_misaligned(tables)) return PZ_E_ALIGN;
     if (n == 0) return PZ_OK;
@@ -2648,7 +2693,7 @@ int pz_step_many(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg
     if (k < 1) return PZ_E_SIZE;
     // the tape is parked from int32 rows (the header says how a caller brings another element type)
     if (cfg->action_format != PZ_ACT_I32) return PZ_E_CONFIG;
-    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (cfg->normalize_obs == 2 ? 7 : 3)) != 0))
+    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (rows16(cfg->normalize_obs) ? 7 : 3)) != 0))
         return PZ_E_ALIGN;
     if (tables_misaligned(tables)) return PZ_E_ALIGN;
     if (n == 0) return PZ_OK;

@@ -37,6 +37,12 @@ AGENTS = ["player_1", "player_2"]
 
 # action vectors a step launch reads as they are (pz_action_format); any other integer dtype is widened on the host
 _ACTION_FORMAT = {torch.int32: 0, torch.int64: 1, torch.uint8: 2, torch.int16: 3}
+# observation_dtype -> pz_config.normalize_obs (include/pikazoo_hip.h enum pz_obs_format; 1 / 5 / 6 are the fused
+# NormalizeObservation's float32 / float16 / bfloat16 rows); the row dtype of every format
+_OBS_FORMATS = {torch.int32: 0, torch.int16: 2, torch.float16: 3, torch.bfloat16: 4}
+_OBS_DTYPES = (torch.int32, torch.float32, torch.int16, torch.float16, torch.bfloat16, torch.float16, torch.bfloat16)
+_OBS_NORMALIZED = {0: 1, 3: 5, 4: 6}  # what fusing NormalizeObservation makes of a format (int16: not fused)
+_OBS_FLOAT16 = (3, 4, 5, 6)
 # flight_tables= of the env -> (landing table, power-hit table)
 _TABLE_MODES = {True: (True, True), "both": (True, True), "power_hit": (False, True),
                 False: (False, False), None: (False, False), "none": (False, False)}
@@ -167,7 +173,12 @@ class raw_env(ParallelEnv):
     the constructor then draws 40 values behind the two boldness draws and every ``render()`` advances the RNG of the
     games it draws; ``observation_dtype`` (``torch.int32``: the reference's Box dtype; ``torch.int16``: the same
     values in half the bytes -- observations are the largest stream a step writes, so large batches run up to a third
-    faster again; the fused ``NormalizeObservation`` emits float32 and cannot be combined with it).  With ``scenery``
+    faster again; the fused ``NormalizeObservation`` emits float32 and cannot be combined with it; ``torch.float16`` /
+    ``torch.bfloat16`` (or their names): the same 70-byte rows as float values for a half-precision policy -- the int32
+    values converted (exact in float16; bfloat16 rounds to nearest even above 256), and with the fused
+    ``NormalizeObservation`` its float32 rows rounded to float16 / bfloat16.  An observation-reading wrapper that would
+    run outside the kernel on such rows is refused (ValueError); bfloat16 has no numpy dtype: its Box reports float32,
+    and ``scalar_api`` refuses it).  With ``scenery``
     the punch effect is drawn too: its two ball attributes are tracked after every ``step()``, a k-frame
     launch clears it; off by default, which keeps ``render()`` free of side effects and ``step()`` a single launch).
 
@@ -202,10 +213,12 @@ class raw_env(ParallelEnv):
             raise ValueError("num_envs must be >= 1")
         if state_format not in ("int32", "packed"):
             raise ValueError('state_format must be "int32" or "packed"')
-        if observation_dtype in ("int16", "int32"):
+        if observation_dtype in ("int16", "int32", "float16", "bfloat16"):
             observation_dtype = getattr(torch, observation_dtype)
-        if observation_dtype not in (torch.int32, torch.int16):
-            raise ValueError("observation_dtype must be torch.int32 or torch.int16")
+        if observation_dtype not in _OBS_FORMATS:
+            raise ValueError("observation_dtype must be torch.int32, torch.int16, torch.float16 or torch.bfloat16")
+        if scalar_api and observation_dtype == torch.bfloat16:
+            raise ValueError("scalar_api returns numpy rows, and numpy has no bfloat16: use torch.float16 or an integer dtype")
         if scenery and render_mode is None:
             raise ValueError('scenery=True needs render_mode="rgb_array"')
         if state_format == "packed" and int(winning_score) > 32767:
@@ -254,7 +267,7 @@ class raw_env(ParallelEnv):
         cfg.x_line, cfg.y_line = 216, 176
         cfg.auto_reset = int(self.auto_reset)
         cfg.packed_state = int(state_format == "packed")
-        cfg.normalize_obs = 2 if observation_dtype == torch.int16 else 0  # 0 int32, 1 float32 normalized, 2 int16
+        cfg.normalize_obs = _OBS_FORMATS[observation_dtype]  # include/pikazoo_hip.h enum pz_obs_format
         cfg.seed = self.seed & 0xFFFFFFFFFFFFFFFF
         cfg.env_id_base = self.env_id_base
         # validate_actions: the step kernels count out-of-range actions into this device word (pz_config.action_faults);
@@ -494,7 +507,7 @@ class raw_env(ParallelEnv):
         # not as a kernel branch: a second RewardByBallPosition; above NormalizeObservation (it then reads the NORMALIZED
         # ball coordinates, reward_by_ball_position.py:22 -- what the reference does, and what the wrapper class then
         # does); above statistics that already sum a wrapped reward; above a reward wrapper that runs outside the kernel
-        if self._cfg.ballpos_reward or self._cfg.normalize_obs == 1 or self._cfg.episode_stats_mode == 2 or \
+        if self._cfg.ballpos_reward or self._cfg.normalize_obs in (1, 5, 6) or self._cfg.episode_stats_mode == 2 or \
                 self._unfused_reward or "NormalizeObservation" in self._unfused:
             return False
         self._cfg.ballpos_reward = 1
@@ -515,15 +528,25 @@ class raw_env(ParallelEnv):
         return True
 
     def _fuse_normalize_obs(self) -> bool:
-        """wrappers/normalize_observation.py:18-35 inside the kernel: observations become float32."""
-        if self._cfg.normalize_obs != 0 or "NormalizeObservation" in self._unfused or "RewardByBallPosition" in self._unfused:
+        """wrappers/normalize_observation.py:18-35 inside the kernel: observations become float32 (float16 / bfloat16
+        rows: the float32 quotient rounded to that type)."""
+        fmt = self._cfg.normalize_obs
+        if fmt not in _OBS_NORMALIZED or "NormalizeObservation" in self._unfused or "RewardByBallPosition" in self._unfused:
             # already normalized; int16 observations (the kernel's float32 rows need the int32 buffers); or a
             # RewardByBallPosition BELOW this wrapper runs outside the kernel and reads the raw coordinates from the
             # observations the kernel hands it (fused, the normalization would move below it)
             return False
-        self._cfg.normalize_obs = 1
+        self._cfg.normalize_obs = _OBS_NORMALIZED[fmt]
         self._cfg_version += 1
         return True
+
+    def _refuse_unfused_on_float16(self, name: str, why: str):
+        """A wrapper that reads observations cannot run outside the kernel on float16 / bfloat16 rows: it would compute
+        on the rounded values and deviate from the reference without a warning."""
+        if self._cfg.normalize_obs in _OBS_FLOAT16:
+            raise ValueError(f"{name} cannot be fused here ({why}) and would then read the {self.obs_dtype} observation "
+                             "rows outside the kernel, i.e. compute on rounded values that differ from the reference: "
+                             "use observation_dtype torch.int32 or torch.int16 for this wrapper stack")
 
     def _fuse_episode_stats(self) -> bool:
         """wrappers/record_episode_statistics.py:27-40 inside the kernel (three words per game)."""
@@ -563,11 +586,12 @@ class raw_env(ParallelEnv):
 
     @property
     def obs_dtype(self):
-        return (torch.int32, torch.float32, torch.int16)[self._cfg.normalize_obs]
+        return _OBS_DTYPES[self._cfg.normalize_obs]
 
     def _obs_view(self, i, buf=None):
         """The env-owned observation buffer of agent i (or `buf`, an int32 [n, 35] buffer) in the current format: the
-        int16 rows occupy the front of the same storage (an even number of them: include/pikazoo_hip.h)."""
+        2-byte rows (int16 / float16 / bfloat16) occupy the front of the same storage (an even number of them:
+        include/pikazoo_hip.h)."""
         buf = self._obs[i] if buf is None else buf
         fmt = self._cfg.normalize_obs
         if fmt == 0:
@@ -575,22 +599,27 @@ class raw_env(ParallelEnv):
         if fmt == 1:
             return buf.view(torch.float32)
         n = self.num_envs
-        return buf.view(torch.int16).view(-1)[:(n + 1) // 2 * 2 * _native.OBS_DIM].view(-1, _native.OBS_DIM)[:n]
+        rows = buf.view(torch.int16).view(-1)[:(n + 1) // 2 * 2 * _native.OBS_DIM].view(-1, _native.OBS_DIM)[:n]
+        return rows if fmt == 2 else rows.view(_OBS_DTYPES[fmt])
 
     # ---- spaces (pikazoo_env.py:481-568) ----------------------------------------------------------
     def observation_space(self, agent=None):
         # the reference lru_caches this method (pikazoo_env.py:481): same object on every call; cached per
         # instance here (an lru_cache on the method would pin the env and its device tensors forever)
+        # (bfloat16 rows: numpy has no bfloat16, the Box reports float32 -- every bound is exact in both)
         sp = self._spaces.get("obs")
         if sp is None:
-            dt = np.int16 if self._cfg.normalize_obs == 2 else np.int32
+            dt = {2: np.int16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32}.get(self._cfg.normalize_obs,
+                                                                                              np.int32)
             sp = self._spaces["obs"] = Box(low=OBS_LOW.astype(dt), high=OBS_HIGH.astype(dt), shape=(35,), dtype=dt)
         return sp
 
     def normalized_observation_space(self, agent=None):
+        # float16 rows: Box(0, 1, float16); bfloat16 rows report float32 like observation_space
         sp = self._spaces.get("norm")
         if sp is None:  # normalize_observation.py:35
-            sp = self._spaces["norm"] = Box(low=0.0, high=1.0, shape=(35,), dtype=np.float32)
+            dt = np.float16 if self._cfg.normalize_obs in (3, 5) else np.float32
+            sp = self._spaces["norm"] = Box(low=0.0, high=1.0, shape=(35,), dtype=dt)
         return sp
 
     def action_space(self, agent):
@@ -906,7 +935,10 @@ class raw_env(ParallelEnv):
         """The output tensors of a k-frame launch; the two observation tensors in different ranks of the device
         memory when they are large enough for that to matter (placement.alloc_pair)."""
         n, dev = self.num_envs, self.device
-        shape = (k, n, _native.OBS_DIM)
+        # 2-byte rows: a frame holds an even number of rows (the launch writes the padding row of an odd n; k > 1 needs
+        # n % 8 == 0, so only a single-frame trajectory has one)
+        rows = (n + 1) // 2 * 2 if self._cfg.normalize_obs >= 2 else n
+        shape = (k, rows, _native.OBS_DIM)
         if self._place_trajectories:
             from . import placement
 
@@ -915,16 +947,18 @@ class raw_env(ParallelEnv):
             self.trajectory_placement = dict(placement.last_info)
         else:
             obs = [torch.empty(shape, dtype=self._traj_obs_dtype(), device=dev) for _ in range(2)]
+        obs = [o[:, :n] for o in obs]
         return {"_k": k, "_obs": obs,
                 "_rew": [torch.empty((k, n), dtype=torch.int32, device=dev) for _ in range(2)],
                 "_term": torch.empty((k, n), dtype=torch.uint8, device=dev)}
 
     def _traj_multiple(self):
         """every frame's observation slab of a trajectory launch must stay 16-byte aligned: 140- resp. 70-byte rows"""
-        return 8 if self._cfg.normalize_obs == 2 else 4
+        return 8 if self._cfg.normalize_obs >= 2 else 4
 
     def _traj_obs_dtype(self):
-        return torch.int16 if self._cfg.normalize_obs == 2 else torch.int32
+        # (the 2-byte rows are viewed as their dtype by _finish_trajectory)
+        return torch.int16 if self._cfg.normalize_obs >= 2 else torch.int32
 
     def _finish_trajectory(self, out):
         self._next_outputs()
@@ -979,7 +1013,8 @@ class raw_env(ParallelEnv):
 
     def _cfg_dict(self):
         d = {k: getattr(self._cfg, k) for k in self._CFG_KEYS}
-        d["normalize_obs"] = int(self._cfg.normalize_obs == 1)  # (int32 vs int16 observations: same trajectory)
+        # normalized or not: the row dtype (int32 / int16 / float16 / bfloat16) does not change the trajectory
+        d["normalize_obs"] = int(self._cfg.normalize_obs in (1, 5, 6))
         d["additional_reward"] = [float(v) for v in self._cfg.additional_reward]
         return d
 

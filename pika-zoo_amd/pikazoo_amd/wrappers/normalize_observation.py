@@ -5,10 +5,15 @@ Observations become ``float32`` ``(obs - low) / (high - low)`` with the bounds o
 can consume them without a cast).  The reference divides in float64 and declares a float32 Box; the
 kernel's IEEE float32 quotient equals the float32 rounding of that double for every reachable value.
 
+With ``observation_dtype=torch.float16`` / ``torch.bfloat16`` the fused rows are that float32 quotient rounded to
+nearest even to float16 / bfloat16 (``observation_space``: ``Box(0, 1, float16)``; bfloat16 reports float32, numpy
+having no bfloat16).
+
 Outside the kernel (``fused`` False) in two cases: the env was created with ``observation_dtype=torch.int16`` (the
 kernel's float32 rows need the int32 buffers) -- the same quotient is then taken here; and a second instance, whose
 bounds are the first one's Box(0, 1) (normalize_observation.py:15-16 reads the WRAPPED env's space): ``(obs - 0) / (1 - 0)``,
-the identity.
+the identity.  On float16 / bfloat16 rows neither is allowed -- the quotient would be taken of rounded values -- and
+the constructor raises ValueError: a second instance, or one above a RewardByBallPosition that runs outside the kernel.
 """
 from __future__ import annotations
 
@@ -25,6 +30,8 @@ class NormalizeObservation(BaseParallelWrapper):
         self.low = {a: env.observation_space(a).low for a in raw.possible_agents}
         self.fused = raw._fuse_normalize_obs()
         if not self.fused:
+            raw._refuse_unfused_on_float16("NormalizeObservation", "a second one, or one above a RewardByBallPosition that "
+                                           "runs outside the kernel")
             raw._note_unfused("NormalizeObservation")
             self._lo = {a: torch.as_tensor(self.low[a], dtype=torch.float32, device=raw.device) for a in raw.possible_agents}
             self._range = {a: torch.as_tensor(self.high[a], dtype=torch.float32, device=raw.device) - self._lo[a]
@@ -46,4 +53,4 @@ class NormalizeObservation(BaseParallelWrapper):
         return (self._normalize(out[0]),) + tuple(out[1:])
 
     def observation_space(self, agent):
-        return self.env.unwrapped.normalized_observation_space(agent)  # Box(0, 1, (35,), float32)
+        return self.env.unwrapped.normalized_observation_space(agent)  # Box(0, 1, (35,), float32 / float16)

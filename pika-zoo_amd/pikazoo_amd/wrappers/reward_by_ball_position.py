@@ -8,7 +8,9 @@ Normally **fused**: the add runs in the step kernel's epilogue in float32, so th
 ``float32[num_envs]``.  Where the stack order cannot be a kernel branch -- a second RewardByBallPosition, one above
 ``NormalizeObservation`` (which, as in the reference, then compares the NORMALIZED coordinates ``obs[26], obs[27]`` with
 the lines, :22-24), one above statistics of a wrapped reward or above another wrapper that runs outside the kernel -- the
-same three lines run here on the step's outputs (``fused`` is False), float32 like the fused form.
+same three lines run here on the step's outputs (``fused`` is False), float32 like the fused form -- but not on
+float16 / bfloat16 observation rows, where the constructor raises ValueError instead (the comparison would read
+rounded coordinates).
 """
 from __future__ import annotations
 
@@ -27,6 +29,8 @@ class RewardByBallPosition(BaseParallelWrapper):
         raw = env.unwrapped
         self.fused = raw._fuse_ballpos_reward(additional_reward, x_line, y_line)
         if not self.fused:
+            raw._refuse_unfused_on_float16("RewardByBallPosition", "a second one, one above NormalizeObservation, above "
+                                           "statistics of a wrapped reward or above a wrapper that runs outside the kernel")
             raw._note_unfused("RewardByBallPosition", reward=True)
             self._table = torch.tensor([float(v) for v in additional_reward], dtype=torch.float32, device=raw.device).view(2, 4)
 
