@@ -141,8 +141,8 @@ typedef struct pz_config {
                                      shifts bit tables): that game's input for the frame is undefined, no memory is
                                      touched out of bounds, every other game is unaffected.  With NULL nothing is
                                      checked (the range is then the caller's contract, as in ABI 7). */
-    int32_t action_format;        /* enum pz_action_format: element type of act_p1 / act_p2 (pz_step, pz_step_bound) and of
-                                     the tape of pz_step_many (PZ_ACT_I32 or PZ_ACT_I64 there) */
+    int32_t action_format;        /* enum pz_action_format: element type of act_p1 / act_p2 (pz_step, pz_step_bound); the
+                                     tape of pz_step_many is int32 alone (PZ_ACT_I32, else PZ_E_CONFIG) */
     int32_t reserved0;            /* 0 */
 } pz_config;
 
@@ -309,9 +309,10 @@ int pz_rollout_random(int32_t *state, int64_t n, int64_t stride, const pz_config
                       const pz_flight_tables *tables, void *stream);
 
 /* ---- k frames of GIVEN actions in one launch, every frame's outputs kept -------------------
- * actions: int32[k][2][n] (frame, agent, game), or int64[k][2][n] with cfg->action_format = PZ_ACT_I64 (the other
- * formats: PZ_E_CONFIG -- widen a uint8 / int16 tape to int32 first, which cannot wrap) -- e.g. a recorded action tape
- * or an open-loop plan; outputs as in pz_rollout_random.  Identical to k calls of pz_step on the k slices.
+ * actions: int32[k][2][n] (frame, agent, game), cfg->action_format = PZ_ACT_I32 (any other format: PZ_E_CONFIG --
+ * widen a uint8 / int16 tape to int32 first, which cannot wrap, and range-check an int64 tape before narrowing it) --
+ * e.g. a recorded action tape or an open-loop plan; outputs as in pz_rollout_random.  Identical to k calls of pz_step on
+ * the k slices.
  * n must be a multiple of 4 when k > 1. */
 int pz_step_many(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
                  const void *actions, int32_t k,

@@ -54,6 +54,30 @@ class WrappedOracle:
     def raw_state(self):
         return self.env.state
 
+    def plant(self, state):
+        """Start from ``state`` (int32 [44, n], e.g. a batch's planted states) instead of ``reset()``: a game planted
+        over is reset right before its first step, like any finished game; every RecordEpisodeStatistics starts at 0."""
+        self.env.state[:] = state
+        for (name, _), st in zip(self.stack, self.state):
+            if name == "RecordEpisodeStatistics":
+                st["r"][:] = 0.0
+                st["l"][:] = 0
+        self._ended = self.env.state[po.E_GAME_ENDED] != 0
+
+    def _outermost_stats(self):
+        st = [st for (name, _), st in zip(self.stack, self.state) if name == "RecordEpisodeStatistics"]
+        assert st, "no RecordEpisodeStatistics in the stack"
+        return st[-1]
+
+    @property
+    def episode_returns(self):
+        """float64 [2, n]: the running returns of the outermost RecordEpisodeStatistics"""
+        return self._outermost_stats()["r"]
+
+    @property
+    def episode_lengths(self):
+        return self._outermost_stats()["l"]
+
     def _obs_out(self, obs):
         o = [obs[0].astype(np.float64), obs[1].astype(np.float64)]
         integral = True

@@ -690,6 +690,7 @@ def test_kernel_matrix_names_exactly_the_step_kernels_in_the_library(built_lib):
     instantiation added without a row, a row naming a kernel the library does not hold, and an instantiation left in
     the library that no launch can reach all fail here."""
     sys.path.insert(0, str(REPO / "tools"))
+    import kernel_configs
     import kernel_digest
     import kernel_matrix
 
@@ -705,8 +706,8 @@ def test_kernel_matrix_names_exactly_the_step_kernels_in_the_library(built_lib):
     # every row's kernel is the one the restated dispatch picks for its configuration; a computer player's kernel on the
     # flight tables runs under both table modes
     for row in kernel_matrix.ROWS:
-        assert kernel_matrix.dispatch(row.entry, row.k, row.n, row.packed, row.obs16, row.plain, row.tables, row.p1,
-                                      row.p2) == row.kernel, row.id
+        assert kernel_matrix.dispatch(row.entry, row.k, row.n, row.cfg, row.stats, row.tables) == row.kernel, row.id
+        assert kernel_configs.is_plain(row.cfg, row.stats) == row.plain, row.id
         assert row.above == (row.n >= kernel_matrix.SWITCH) and row.n % 8 == 0 and row.stride > row.n
     ids = [row.id for row in kernel_matrix.ROWS]
     assert len(ids) == len(set(ids))

@@ -17,6 +17,7 @@ import torch
 from torch.profiler import ProfilerActivity, profile
 
 import kernel_matrix as km
+from kernel_configs import config_fields
 from test_gpu_packed import _random_valid_states
 from test_gpu_parity import make_env
 
@@ -110,7 +111,8 @@ def _float16_instantiations():
         if tables != "none" and not (ai1 or ai2):
             continue
         n = km.N_ABOVE if above else km.N_BELOW
-        name = km.dispatch(entry, k, n, packed, True, False, tables, ai1, ai2)
+        cfg = config_fields(p1_computer=ai1, p2_computer=ai2, packed_state=packed, normalize_obs=3)
+        name = km.dispatch(entry, k, n, cfg, False, tables)
         seen.setdefault(name, (entry, k, n, packed, ai1, ai2, tables))
     return seen
 
