@@ -26,7 +26,7 @@ DIAG_LIB = LIB_DIR / "libpikazoo_diag.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
 DEPS = SOURCES + DIAG_SOURCES + [CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp",
-                                 INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h"]
+                                 CSRC / "pz_dispatch.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]

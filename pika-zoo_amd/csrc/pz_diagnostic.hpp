@@ -13,8 +13,9 @@
 //                profiles/r05_experiments/early_store_edge_partner_held_back.log)
 //   bit 5        no early stores at all
 //   bits 8-15    hold the computer's wave back N x 127 sleep cycles in front of its first load
-//   bits 16-29   keep only a subset of the step kernels' instantiations (dev_keep in pz_kernels.hip): a variant that is
-//                timed on one configuration builds in seconds instead of the 100 s of the full library; 0 = all
+//   bits 16-29   keep only a subset of the step kernels' instantiations (dev_keep in pz_kernels.hip, applied to the image
+//                of the choice in pz_dispatch.hpp): a variant that is timed on one configuration builds in seconds
+//                instead of the 100 s of the full library; 0 = all
 // Closed experiments are not switches any more: their measured value is a constexpr beside the one-line result
 // (pz_kernels.hip, pz_memory.hpp), the logs are under profiles/.
 #pragma once

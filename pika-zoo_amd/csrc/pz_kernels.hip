@@ -22,9 +22,12 @@
 // column accesses, and rows past the end of the batch are dropped by the hardware range check.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 #include "pikazoo_hip.h"
+#include "pz_dispatch.hpp"
 #include "pz_physics.hpp"
 #include "pz_packed.hpp"
 #include "pz_memory.hpp"
@@ -42,12 +45,7 @@ constexpr int kTrajAux = 19;
 // the k-frame launches' rewards / flags / actions (17 of a game-step's 297 bytes): sc1 nt where the launch gathers
 // from the flight tables (3.13 -> 3.11 us per frame, k = 128: 2.99 -> 2.94), plain otherwise (nt: 2.81 -> 2.94)
 constexpr int traj_small_aux(bool computer_player) { return computer_player ? 18 : 0; }
-// launch_step_players: the human-vs-human rollout on one wave keeps its generic kernel -- it runs at the write ceiling of
-// its two tensors either way and its leaner PLAIN form measured 0.6-3.4 % slower (profiles/r04_experiments/ab_rollout_hh_*)
-constexpr bool kHhRolloutGeneric = true;
-// launch_step: which human-vs-human k-frame launches run on two waves per 64 games: 1 = those on int16 rows (2.47 -> 2.23 us
-// per frame), 2 = all (3.62 vs 3.63 on one wave: no gain; profiles/r03_experiments/)
-constexpr int kHhPairRollout = 1;
+// (which kernel a launch runs -- pair or single wave, PLAIN or generic: pz_dispatch.hpp, beside its measurements)
 // pair_body: what the human player's wave of a one-computer launch stores in front of the exchange barrier: 2 = its own
 // player's columns and the ball's position / trail / rotation (8.62 -> 8.46 us per launch behind the LDS hand-shake,
 // profiles/r05_experiments/ab_early_store_edge_*.log); 0 = nothing
@@ -539,7 +537,7 @@ __device__ __forceinline__ void flush_obs(const int32_t* __restrict__ lds, void*
 // PLAIN launches (k-frame kernels): no fused wrapper, no episode statistics, raw integer rows.  The configuration words
 // of those features then read as compile-time constants, and their branches -- with the scalars and lane masks the
 // compiler would otherwise carry around the frame loop for them (the reward table alone is eight SGPRs of a budget of
-// ~100) -- leave the kernel.  The host picks the PLAIN instantiation when the configuration allows (launch_step).
+// ~100) -- leave the kernel.  The host picks the PLAIN instantiation when the configuration allows (pz_dispatch.hpp).
 template <bool PLAIN, bool OBS16>
 __device__ __forceinline__ StepArgs effective_args(const StepArgs& in)
 {
@@ -566,7 +564,7 @@ __device__ __forceinline__ StepArgs effective_args(const StepArgs& in)
 //       kTape     -- the same with the actions of every frame read from an int32[k][2][n] tape
 //                    (pz_step_many), parked in LDS one byte per action, 64 frames per fetch.
 // SPARSE: changed-only write-back of the rarely changing columns (large batches).
-enum StepMode { kActions = 0, kRandom = 1, kRollout = 2, kTape = 3 };
+// (enum StepMode, and which instantiation a launch runs: pz_dispatch.hpp)
 // pz_step_many parks its action tape in LDS, ONE BYTE per action (an action is < 18; an out-of-range one was counted
 // while it was parked, include/pikazoo_hip.h): kTapeChunk frames of both players for a wave's 64 games are 8 KB.
 constexpr int kTapeChunk = 64;                       // frames of the action tape fetched at once by pz_step_many (16: 3.88 vs 3.27 us per frame)
@@ -2215,27 +2213,6 @@ __global__ __launch_bounds__(256) void render_kernel(const int32_t* __restrict__
 // Buffer descriptors address with 32-bit byte offsets: one launch handles at most this many games
 // (4 GiB / 176 B of state per game); larger jobs are sharded by the caller (env_id_base).
 constexpr int64_t kMaxLanesPerLaunch = (int64_t)0xFFFFFFFFu / (PZ_STATE_WORDS * 4);
-// batches from this size on are HBM-bound and use the changed-only write-back
-// Kernel selection by batch size (interleaved A/B on MI355X, tools/ab.py; us per pz_step launch):
-//   human-vs-human, pair kernel | single-wave kernel, both with the changed-only write-back:
-//       65 536: 7.58 | 8.01    131 072: 11.1 | 11.5    262 144: 22.4 | 23.8    294 912: 25.3 | 26.5
-//      524 288: 47.2 | 46.5    1 048 576: 93.9 | 90.6      (single-wave without changed-only at 65 536: 8.52)
-//   player 2 = computer, scout kernel | single-wave changed-only:   262 144: 36.5 | 38.2    524 288: 70.3 | 66.4
-constexpr int64_t kTwoWaveMaxLanes = 393216;  // below: two waves per workgroup (pair kernel / scout)
-//   the changed-only write-back also pays in the scout kernel (65 536: 14.3 | 14.65 without, 262 144: 35.6 | 36.6)
-//   and is used by every launch that writes the state back after ONE frame; a trajectory launch writes it once
-//   per k frames, where the plain write-back is always right.
-
-static inline bool is_packed(const pz_config& cfg) { return (cfg.packed_state & 1) != 0; }
-// formats 2 - 6 (int16 / float16 / bfloat16): 70-byte rows, an even number per frame (the OBS16 instantiations)
-static inline bool rows16(int format) { return format >= PZ_OBS_I16; }
-// no fused wrapper, no episode statistics, raw integer rows: what the PLAIN k-frame kernels are compiled for
-static inline bool is_plain(const StepArgs& a)
-{
-    return a.cfg.simplify_action == 0 && a.cfg.ballpos_reward == 0 && a.cfg.normal_state_mode == 0 &&
-           (a.cfg.normalize_obs == PZ_OBS_I32 || a.cfg.normalize_obs == PZ_OBS_I16) &&
-           (a.cfg.episode_stats_mode == 0 || a.episode_stats == nullptr);
-}
 static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 static int check_common(const void* state, int64_t n, int64_t stride, const pz_config* cfg)
@@ -2263,182 +2240,61 @@ static inline unsigned int blocks_for(int64_t n, int per) { return (unsigned int
 // 4: the packed state format; 5: int16 rows; 6: human vs human; 7: player 2 = computer; 8: the other computer-player
 // combinations; 9: step_pair_kernel; 10: rollout_pair_kernel; 11: step_kernel; 12: the PLAIN forms of the k-frame
 // kernels; 13: their generic forms.  A launch that was left out returns PZ_E_CONFIG.
-enum DevFamily { kDevPair = 9, kDevRolloutPair = 10, kDevSingle = 11 };
-constexpr bool dev_keep(int family, int mode, bool ai1, bool ai2, bool packed, bool obs16, bool plain = false)
+constexpr bool dev_keep(const StepKernel& s)
 {
     constexpr unsigned m = diag::kSubset;
     if (m == 0u) return true;
-    const bool players = (!ai1 && !ai2) ? (m >> 6) & 1u : ((!ai1 && ai2) ? (m >> 7) & 1u : (m >> 8) & 1u);
-    const bool form = (mode != kRollout && mode != kTape) || ((m >> (plain ? 12 : 13)) & 1u);
-    return ((m >> family) & 1u) && ((m >> mode) & 1u) && players && (!packed || ((m >> 4) & 1u)) &&
-           (!obs16 || ((m >> 5) & 1u)) && form;
-}
-#define PZ_KEEP(...) pz::dev_keep(__VA_ARGS__)
-// instantiations no launch of the product can reach are not built (a branch to one returns PZ_E_CONFIG, as a dev_keep
-// exclusion does): human vs human takes the pair rollout only on int16 rows (kHhPairRollout == 1), and a packed
-// human-vs-human pz_step always takes step_pair_kernel -- but for the diagnostic builds without it (diag::kNoPairKernel)
-constexpr bool rollout_pair_reachable(bool ai1, bool ai2, bool obs16) { return ai1 || ai2 || obs16 || kHhPairRollout == 2; }
-constexpr bool single_reachable(int mode, bool ai1, bool ai2, bool packed)
-{
-    return ai1 || ai2 || !packed || mode != kActions || diag::kNoPairKernel;
+    const bool players = (!s.ai1 && !s.ai2) ? (m >> 6) & 1u : ((!s.ai1 && s.ai2) ? (m >> 7) & 1u : (m >> 8) & 1u);
+    const bool form = (s.mode != kRollout && s.mode != kTape) || ((m >> (s.plain ? 12 : 13)) & 1u);
+    return ((m >> (9 + s.family)) & 1u) && ((m >> s.mode) & 1u) && players && (!s.packed || ((m >> 4) & 1u)) &&
+           (!s.obs16 || ((m >> 5) & 1u)) && form;
 }
 
-// one step_kernel instantiation per player configuration; the trajectory modes also per observation row format
-// (OBS16, compile-time there: see TrajOut::flush)
-template <int MODE, bool SPARSE, int SCOUT, bool PACKED, bool OBS16>
-static int launch_step_players(const StepArgs& a, hipStream_t stream)
+// the instantiations built: the image of the choice under this build's switches, less a diagnostic subset's exclusions
+constexpr LeftOut kLeftOut{diag::kNoPairKernel, diag::kNoRolloutPair, diag::kNoScoutWave};
+constexpr StepKernelSet built_step_kernels()
 {
-    const dim3 grid(blocks_for(a.n, kLanes)), block(SCOUT != kNoScout ? 2 * kLanes : kLanes);
-    const bool ai1 = a.cfg.p1_computer != 0, ai2 = a.cfg.p2_computer != 0;
-    // the k-frame launches of a configuration without fused wrappers / statistics: the PLAIN instantiation (effective_args)
-    // -- but for the human-vs-human rollout on one wave: that launch runs at the write ceiling of the two observation
-    // tensors either way, and its leaner PLAIN form (6 SGPR spills instead of 53) measured 0.6 - 3.4 % SLOWER there,
-    // on every box and in every position of the interleaved rounds (us per frame, k = 32: 2.91 vs 2.81-2.84; k = 128:
-    // 2.73 vs 2.65; store order within the frame: no effect; profiles/r04_experiments/ab_rollout_hh_*), while the tape
-    // kernel and every computer-player launch gain 1-2 % from theirs
-    constexpr bool kHasPlain = (MODE == kRollout || MODE == kTape) && SCOUT == kNoScout && !PACKED;
-    const bool plain = kHasPlain && is_plain(a);
-#define PZ_PLAIN_HERE(A1, A2) (kHasPlain && !(kHhRolloutGeneric && MODE == kRollout && !(A1) && !(A2)))
-#define PZ_LAUNCH_SINGLE_AS(A1, A2, PLAIN)                                                                                \
-    do {                                                                                                                  \
-        if constexpr (PZ_KEEP(kDevSingle, MODE, A1, A2, PACKED, OBS16, PLAIN) && single_reachable(MODE, A1, A2, PACKED))   \
-            hipLaunchKernelGGL((step_kernel<A1, A2, MODE, SPARSE, SCOUT, PACKED, OBS16, PLAIN>), grid, block, 0, stream,   \
-                               PZ_HOT_ARGS(a), a);                                                                        \
-        else                                                                                                              \
-            return PZ_E_CONFIG;                                                                                           \
-    } while (0)
-#define PZ_LAUNCH_SINGLE(A1, A2)                                                                                          \
-    do {                                                                                                                  \
-        if constexpr (PZ_PLAIN_HERE(A1, A2)) {                                                                            \
-            if (plain) {                                                                                                  \
-                PZ_LAUNCH_SINGLE_AS(A1, A2, true);                                                                        \
-                break;                                                                                                    \
-            }                                                                                                             \
-        }                                                                                                                 \
-        PZ_LAUNCH_SINGLE_AS(A1, A2, false);                                                                               \
-    } while (0)
-    if (ai1 && ai2)
-        PZ_LAUNCH_SINGLE(true, true);
-    else if (ai1)
-        PZ_LAUNCH_SINGLE(true, false);
-    else if (ai2)
-        PZ_LAUNCH_SINGLE(false, true);
-    else if constexpr (SCOUT == kNoScout)  // (a scout wave only ever serves a computer player)
-        PZ_LAUNCH_SINGLE(false, false);
-#undef PZ_LAUNCH_SINGLE
-#undef PZ_LAUNCH_SINGLE_AS
-#undef PZ_PLAIN_HERE
+    const StepKernelSet image = step_kernel_image(kLeftOut);
+    StepKernelSet kept{};
+    for (int i = 0; i < image.count; ++i)
+        if (dev_keep(image.at[i])) kept.at[kept.count++] = image.at[i];
+    return kept;
+}
+constexpr StepKernelSet kBuilt = built_step_kernels();
+
+// every step kernel takes the same arguments: one table of them, indexed by code() (nullptr: not built)
+using StepKernelFn = void (*)(PZ_HOT_PARAMS, const StepArgs);
+template <int I>
+constexpr StepKernelFn built_kernel()
+{
+    constexpr StepKernel s = kBuilt.at[I];
+    if constexpr (s.family == kStepPairKernel)
+        return step_pair_kernel<s.ai1, s.ai2, s.packed, s.mode == kRandom>;
+    else if constexpr (s.family == kRolloutPairKernel)
+        return rollout_pair_kernel<s.ai1, s.ai2, s.mode, s.packed, s.obs16, s.plain>;
+    else
+        return step_kernel<s.ai1, s.ai2, s.mode, s.sparse, s.scout, s.packed, s.obs16, s.plain>;
+}
+template <int... I>
+constexpr std::array<StepKernelFn, kStepKernelCodes> kernel_table(std::integer_sequence<int, I...>)
+{
+    std::array<StepKernelFn, kStepKernelCodes> table{};
+    ((table[code(kBuilt.at[I])] = built_kernel<I>()), ...);
+    return table;
+}
+constexpr auto kStepKernels = kernel_table(std::make_integer_sequence<int, kBuilt.count>());
+
+// every step launch: the choice, then its kernel from the table -- 64 lanes per workgroup for a lone wave, 128 for the
+// pair kernels and a scout wave
+static int launch_step(int mode, const StepArgs& a, hipStream_t stream)
+{
+    const StepKernel s = choose_step_kernel(mode, a.k, a.n, a.cfg, a.episode_stats != nullptr, a.tables.power_hit != nullptr,
+                                            kLeftOut);
+    const StepKernelFn kernel = kStepKernels[code(s)];
+    if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
+    const dim3 grid(blocks_for(a.n, kLanes)), block(s.family == kStepKernel && s.scout == kNoScout ? kLanes : 2 * kLanes);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, PZ_HOT_ARGS(a), a);
     return (int)hipGetLastError();
-}
-
-template <int MODE, bool SPARSE, bool PACKED = false, int SCOUT = kNoScout>
-static int launch_step_ai(const StepArgs& a, hipStream_t stream)
-{
-    if constexpr (MODE == kRollout || MODE == kTape) {
-        if (rows16(a.cfg.normalize_obs)) return launch_step_players<MODE, SPARSE, SCOUT, PACKED, true>(a, stream);
-    }
-    return launch_step_players<MODE, SPARSE, SCOUT, PACKED, false>(a, stream);
-}
-
-template <bool AI1, bool AI2, bool RANDOM = false>
-static int launch_pair(const StepArgs& a, hipStream_t stream)
-{
-    const dim3 grid(blocks_for(a.n, kLanes)), block(2 * kLanes);
-    constexpr int kMode = RANDOM ? kRandom : kActions;
-    if (is_packed(a.cfg)) {
-        if constexpr (PZ_KEEP(kDevPair, kMode, AI1, AI2, true, false))
-            hipLaunchKernelGGL((step_pair_kernel<AI1, AI2, true, RANDOM>), grid, block, 0, stream, PZ_HOT_ARGS(a), a);
-        else
-            return PZ_E_CONFIG;
-    } else {
-        if constexpr (PZ_KEEP(kDevPair, kMode, AI1, AI2, false, false))
-            hipLaunchKernelGGL((step_pair_kernel<AI1, AI2, false, RANDOM>), grid, block, 0, stream, PZ_HOT_ARGS(a), a);
-        else
-            return PZ_E_CONFIG;
-    }
-    return (int)hipGetLastError();
-}
-
-template <int MODE>
-static int launch_step(const StepArgs& a, hipStream_t stream)
-{
-    const bool ai1 = a.cfg.p1_computer != 0, ai2 = a.cfg.p2_computer != 0;
-    // with the power-hit table the six candidate flights of a deciding player are one gather: no scout wave is needed, and
-    // the single frame splits by player.  The landing table is optional on top of it (pz_flight_tables in the header):
-    // without it the landing point is predicted in the kernel (predict_landing_x<true>: the closed-form fast-forward)
-    const bool tables = a.tables.power_hit != nullptr;
-    if constexpr (!diag::kNoPairKernel) {
-        // (the packed format: at every size -- 524 288 games, us per launch, pair | single wave: human 30.25 | 30.13,
-        // player 2 = computer 38.6 | 40.6; 1 048 576 human 56.2 | 56.4)
-        if (MODE == kActions && (a.n < kTwoWaveMaxLanes || is_packed(a.cfg)) && (tables || !(ai1 || ai2))) {
-            if (ai1 && ai2) return launch_pair<true, true>(a, stream);
-            if (ai1) return launch_pair<true, false>(a, stream);
-            if (ai2) return launch_pair<false, true>(a, stream);
-            return launch_pair<false, false>(a, stream);
-        }
-        // one frame of the on-device random policy is the same launch with the policy's Philox block in place of the two
-        // action loads (65 536 games: 8.2 -> 7.0 us against the single-wave kernel)
-        if (MODE == kRandom && a.k == 1 && (a.n < kTwoWaveMaxLanes || is_packed(a.cfg)) && (tables || !(ai1 || ai2))) {
-            if (ai1 && ai2) return launch_pair<true, true, true>(a, stream);
-            if (ai1) return launch_pair<true, false, true>(a, stream);
-            if (ai2) return launch_pair<false, true, true>(a, stream);
-            return launch_pair<false, false, true>(a, stream);
-        }
-    }
-    // pz_rollout_random / pz_step_many with a computer player on the flight tables: two waves per 64 games below the size switch
-    // (interleaved A/B, us per frame at k = 32: 3.49 vs 4.34 on one wave; human vs human the single wave is at the
-    // write ceiling already: 3.62 on two waves -- player 1's writing all outputs -- vs 3.63 on one, 3.76 with the
-    // outputs split between the waves)
-    const bool hh_pair = !(ai1 || ai2) && (kHhPairRollout == 2 || (kHhPairRollout == 1 && rows16(a.cfg.normalize_obs)));
-    if constexpr ((MODE == kRollout || MODE == kTape) && !diag::kNoRolloutPair) if (a.n < kTwoWaveMaxLanes && ((tables && (ai1 || ai2)) || hh_pair)) {
-        const dim3 grid(blocks_for(a.n, kLanes)), block(2 * kLanes);
-        const bool packed = is_packed(a.cfg), obs16 = rows16(a.cfg.normalize_obs), plain = is_plain(a);
-#define PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, PK, O16, PLAIN)                                                                 \
-    do {                                                                                                                  \
-        if constexpr (PZ_KEEP(kDevRolloutPair, MODE, A1, A2, PK, O16, PLAIN) && rollout_pair_reachable(A1, A2, O16))        \
-            hipLaunchKernelGGL((rollout_pair_kernel<A1, A2, MODE, PK, O16, PLAIN>), grid, block, 0, stream,                \
-                               PZ_HOT_ARGS(a), a);                                                                        \
-        else                                                                                                              \
-            return PZ_E_CONFIG;                                                                                           \
-    } while (0)
-#define PZ_LAUNCH_ROLLOUT_PAIR(A1, A2)                                                                                    \
-    do {                                                                                                                  \
-        if (packed && obs16)                                                                                              \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, true, true, false);                                                         \
-        else if (packed)                                                                                                  \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, true, false, false);                                                        \
-        else if (obs16 && plain)                                                                                          \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, false, true, true);                                                         \
-        else if (obs16)                                                                                                   \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, false, true, false);                                                        \
-        else if (plain)                                                                                                   \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, false, false, true);                                                        \
-        else                                                                                                              \
-            PZ_LAUNCH_ROLLOUT_PAIR_AS(A1, A2, false, false, false);                                                       \
-    } while (0)
-        if (ai1 && ai2)
-            PZ_LAUNCH_ROLLOUT_PAIR(true, true);
-        else if (ai1)
-            PZ_LAUNCH_ROLLOUT_PAIR(true, false);
-        else if (ai2)
-            PZ_LAUNCH_ROLLOUT_PAIR(false, true);
-        else
-            PZ_LAUNCH_ROLLOUT_PAIR(false, false);
-#undef PZ_LAUNCH_ROLLOUT_PAIR
-#undef PZ_LAUNCH_ROLLOUT_PAIR_AS
-        return (int)hipGetLastError();
-    }
-    // the packed format: pair kernel above, else one wave per workgroup (a computer player without tables computes its
-    // flights in that wave: no scout)
-    if (is_packed(a.cfg)) return launch_step_ai<MODE, false, true>(a, stream);
-    if constexpr (!diag::kNoScoutWave) {
-        if (a.n < kTwoWaveMaxLanes && !tables) {  // a computer player is present (else: pair kernel above)
-            constexpr int kScout = MODE == kActions ? kScoutLoads : kScoutPosted;
-            constexpr bool kSparse = MODE == kActions || MODE == kRandom;
-            if (ai1 || ai2) return launch_step_ai<MODE, kSparse, false, kScout>(a, stream);
-        }
-    }
-    return launch_step_ai<MODE, MODE == kActions || MODE == kRandom>(a, stream);
 }
 
 // the look-ups load whole dwords / 16-byte rows
@@ -2610,7 +2466,7 @@ int pz_step(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, con
     if (tables_misaligned(tables)) return PZ_E_ALIGN;
     StepArgs a{state,  n,          stride,        act_p1,  act_p2, 0, 0, 1, nullptr, obs_p1, obs_p2, rew_p1,
                rew_p2, terminated, episode_stats, nullptr, tables_of(tables), *cfg};
-    return launch_step<kActions>(a, (hipStream_t)stream);
+    return launch_step(kActions, a, (hipStream_t)stream);
 }
 
 // pz_step with its arguments prepared once: the block holds the StepArgs pz_step would build
@@ -2646,7 +2502,7 @@ int pz_step_bound(const void* bound, const void* act_p1, const void* act_p2, voi
     StepArgs a = b->args;
     a.act_p1 = act_p1;
     a.act_p2 = act_p2;
-    return launch_step<kActions>(a, (hipStream_t)stream);
+    return launch_step(kActions, a, (hipStream_t)stream);
 }
 
 int pz_step_random(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, uint64_t action_seed, uint64_t t0,
@@ -2662,7 +2518,7 @@ int pz_step_random(int32_t* state, int64_t n, int64_t stride, const pz_config* c
     StepArgs a{state,  n,          stride,        nullptr, nullptr, action_seed, t0, k, nullptr, obs_p1, obs_p2, rew_p1,
                rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
                *cfg};
-    return launch_step<kRandom>(a, (hipStream_t)stream);
+    return launch_step(kRandom, a, (hipStream_t)stream);
 }
 
 int pz_rollout_random(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, uint64_t action_seed,
@@ -2681,7 +2537,7 @@ int pz_rollout_random(int32_t* state, int64_t n, int64_t stride, const pz_config
     StepArgs a{state,  n,          stride,        nullptr, nullptr, action_seed, t0, k, actions, obs_p1, obs_p2, rew_p1,
                rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
                *cfg};
-    return launch_step<kRollout>(a, (hipStream_t)stream);
+    return launch_step(kRollout, a, (hipStream_t)stream);
 }
 
 int pz_step_many(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, const void* actions, int32_t k,
@@ -2700,7 +2556,7 @@ int pz_step_many(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg
     StepArgs a{state,  n,          stride,        actions, nullptr, 0, 0, k, nullptr, obs_p1, obs_p2, rew_p1,
                rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
                *cfg};
-    return launch_step<kTape>(a, (hipStream_t)stream);
+    return launch_step(kTape, a, (hipStream_t)stream);
 }
 
 int pz_random_actions(int32_t* act_p1, int32_t* act_p2, int64_t n, int64_t env_id_base, uint64_t action_seed,

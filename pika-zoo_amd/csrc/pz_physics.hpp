@@ -15,6 +15,7 @@
 
 #include "pikazoo_hip.h"
 #include "pz_diagnostic.hpp"
+#include "pz_dispatch.hpp"
 
 namespace pz {
 
@@ -972,7 +973,7 @@ __device__ __forceinline__ void ball_player_collision(Ball& b, bool hit, int pla
 constexpr int kCandPitch = 7;  // six landing points per game, odd pitch
 constexpr int kHitPitch = 5;   // flag, x, y, x velocity, y velocity
 constexpr int kPostPitch = 5;  // need, x, y, |y velocity| (+1: odd pitch)
-enum ScoutMode { kNoScout = 0, kScoutLoads = 1, kScoutPosted = 2 };
+// (enum ScoutMode: pz_dispatch.hpp)
 struct ScoutLink {
     const int32_t* cand;  // LDS [64][kCandPitch]
     int32_t* hits;        // LDS [64][kHitPitch]   (kScoutLoads)

@@ -9,7 +9,7 @@ levels, and which levels each instantiation can take, and generates a determinis
   * on each side of the size switch, every pair of levels of two factors occurs in some configuration;
   * every configuration dispatches the instantiation it is assigned to -- through `dispatch()`, which works the
     PLAIN-or-fused choice of a k-frame launch out of the configuration with `is_plain()` below (the restatement of
-    `is_plain()` in pika-zoo_amd/csrc/pz_kernels.hip), so a configuration the host would send to the other form of a
+    `is_plain()` in pika-zoo_amd/csrc/pz_dispatch.hpp), so a configuration the host would send to the other form of a
     kernel (`episode_stats_mode != 0` with a NULL statistics pointer, say) is tested as such.
 
 tests/test_cabi_and_host.py checks those three rules; tests/test_gpu_kernel_configs.py runs every configuration
@@ -41,7 +41,7 @@ def config_fields(**over) -> dict:
 
 
 def is_plain(cfg, stats: bool) -> bool:
-    """pz_kernels.hip `is_plain()`: no fused wrapper, no statistics, raw integer rows -- what the PLAIN k-frame
+    """pz_dispatch.hpp `is_plain()`: no fused wrapper, no statistics, raw integer rows -- what the PLAIN k-frame
     kernels are compiled for.  `stats`: a statistics pointer is passed (a statistics mode without one is PLAIN)."""
     return (cfg["simplify_action"] == 0 and cfg["ballpos_reward"] == 0 and cfg["normal_state_mode"] == 0 and
             cfg["normalize_obs"] in (OBS_I32, OBS_I16) and (cfg["episode_stats_mode"] == 0 or not stats))

@@ -1,13 +1,14 @@
 """The step-kernel matrix: one launch configuration per step-kernel instantiation of the product library.
 
 The C ABI picks one of the `step_kernel` / `step_pair_kernel` / `rollout_pair_kernel` instantiations at run time
-(`launch_step` / `launch_pair` / `launch_step_players` in pika-zoo_amd/csrc/pz_kernels.hip) from the entry point, the
-batch size (below or at/above `kTwoWaveMaxLanes`), the state format, the observation row type, whether the launch is
-PLAIN (no fused wrapper, no statistics: tests/kernel_configs.py `is_plain()`, worked out from the configuration and the
-statistics pointer), the flight tables passed and the player mix.  `dispatch()` restates that choice;
-`ROWS` walks the configuration space and keeps, for every instantiation reached, the first configuration that reaches
-it (below the switch where one does), and for a computer-player kernel reached on the flight tables a second row on the
-power-hit table alone (the same kernel, other paths inside it).
+(`choose_step_kernel()` in pika-zoo_amd/csrc/pz_dispatch.hpp; the library builds exactly its image) from the entry
+point, the batch size (below or at/above `kTwoWaveMaxLanes`), the state format, the observation row type, whether the
+launch is PLAIN (no fused wrapper, no statistics: tests/kernel_configs.py `is_plain()`, worked out from the configuration
+and the statistics pointer), the flight tables passed and the player mix.  `dispatch()` restates that choice
+independently (tests/test_dispatch_host.py holds the C++ against it on the host); `ROWS` walks the configuration space
+and keeps, for every instantiation reached, the first configuration that reaches it (below the switch where one does),
+and for a computer-player kernel reached on the flight tables a second row on the power-hit table alone (the same
+kernel, other paths inside it).
 
 tests/test_gpu_kernel_matrix.py runs every row through the C ABI against the oracle, under the row's fixed recipe
 (`Row.config()`), and checks the kernel it dispatched by name (tests/kernel_configs.py holds the other runtime
@@ -51,7 +52,7 @@ def _name(family: str, *args) -> str:
 
 
 def dispatch(entry, k, n, cfg, stats, tables) -> str:
-    """The instantiation `launch_step<MODE>` launches for this configuration (product build).  `cfg`: the pz_config
+    """The instantiation `choose_step_kernel()` picks for this configuration (product build).  `cfg`: the pz_config
     words of kernel_configs.config_fields(); `stats`: a statistics pointer is passed; `tables`: TABLE_MODES."""
     mode = _MODE[entry]
     packed, obs16 = bool(cfg["packed_state"]), cfg["normalize_obs"] >= 2  # rows16(): formats 2 - 6
@@ -75,7 +76,7 @@ def dispatch(entry, k, n, cfg, stats, tables) -> str:
     if small and not hit and not human:  # the scout wave computes the flights beside the frame
         scout = _SCOUT_LOADS if mode == _K_ACTIONS else _SCOUT_POSTED
         return _name("step_kernel", ai1, ai2, mode, sparse, scout, False, traj and obs16, False)
-    # one wave; the k-frame launches have a PLAIN form, but for the human-vs-human rollout (kHhRolloutGeneric)
+    # one wave; the k-frame launches have a PLAIN form, but for the human-vs-human rollout (measured slower there)
     plain_form = traj and plain and not (mode == _K_ROLLOUT and human)
     return _name("step_kernel", ai1, ai2, mode, sparse, _NO_SCOUT, False, traj and obs16, plain_form)
 

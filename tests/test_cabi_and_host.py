@@ -671,7 +671,7 @@ def test_no_scratch_and_bounded_scalar_spills_in_the_step_kernels(built_lib, tmp
             assert not any(t.startswith("scratch_") or "s[0:3]" in t for t in ins), f"{name} uses scratch memory"
     # <AI1, AI2, MODE (2 rollout, 3 tape), SPARSE, SCOUT, PACKED, OBS16, PLAIN> / <AI1, AI2, MODE, PACKED, OBS16, PLAIN>
     # (the human-vs-human rollout keeps its generic form -- the PLAIN one is not even instantiated: it measured slower at
-    # that launch's write ceiling, pz_kernels.hip launch_step_players -- with 53 spills where round 3 had 74)
+    # that launch's write ceiling, pz_dispatch.hpp choose_step_kernel -- with 53 spills where round 3 had 74)
     bounds = {"step_kernel<false, false, 2, false, 0, false, false, false>": 60,
               "rollout_pair_kernel<false, true, 2, false, false, true>": 25,
               "step_kernel<false, false, 3, false, 0, false, false, true>": 25,
