@@ -21,6 +21,7 @@ def main():
     # same kwargs as the reference's pikazoo_v0.env(...) + the batched ones
     env = pikazoo_v0.env(winning_score=15, serve="winner", is_player2_computer=True,
                          num_envs=n, device="cuda:0", seed=0, validate_actions=False)
+    # (frame_skip=4 in the line above: the usual action repeat -- every step() then holds its actions for 4 frames)
     env = RecordEpisodeStatistics(NormalizeObservation(SimplifyAction(env)))  # fused into the step kernel
     obs, infos = env.reset()
     print("agents:", env.agents, "| obs", tuple(obs["player_1"].shape), obs["player_1"].dtype,

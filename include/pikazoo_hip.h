@@ -133,7 +133,7 @@ typedef struct pz_config {
     uint64_t seed;                /* Philox4x32-10 key of the env RNG stream */
     int64_t env_id_base;          /* global id of lane 0 (shards of one job use disjoint ranges) */
     uint64_t *action_faults;      /* NULL, or a device counter (caller-owned, 8-byte aligned, zeroed by the caller): the
-                                     launches that READ actions (pz_step, pz_step_bound, pz_step_many) add to it when an
+                                     launches that READ actions (pz_step, pz_step_bound, pz_step_held, pz_step_many) add to it when an
                                      action lies outside [0, 18) -- [0, 13) with simplify_action.  The reference's table
                                      lookup raises IndexError there (pikazoo_env.py:182); a launch cannot raise, so it
                                      counts: non-zero afterwards = some action was out of range (at least one count per
@@ -141,7 +141,7 @@ typedef struct pz_config {
                                      shifts bit tables): that game's input for the frame is undefined, no memory is
                                      touched out of bounds, every other game is unaffected.  With NULL nothing is
                                      checked (the range is then the caller's contract, as in ABI 7). */
-    int32_t action_format;        /* enum pz_action_format: element type of act_p1 / act_p2 (pz_step, pz_step_bound); the
+    int32_t action_format;        /* enum pz_action_format: element type of act_p1 / act_p2 (pz_step, pz_step_bound, pz_step_held); the
                                      tape of pz_step_many is int32 alone (PZ_ACT_I32, else PZ_E_CONFIG) */
     int32_t reserved0;            /* 0 */
 } pz_config;
@@ -316,6 +316,28 @@ int pz_rollout_random(int32_t *state, int64_t n, int64_t stride, const pz_config
  * n must be a multiple of 4 when k > 1. */
 int pz_step_many(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
                  const void *actions, int32_t k,
+                 int32_t *obs_p1, int32_t *obs_p2, void *rew_p1, void *rew_p2,
+                 uint8_t *terminated, void *episode_stats, int64_t *episodes_done,
+                 const pz_flight_tables *tables, void *stream);
+
+/* ---- frame skip: the two GIVEN action vectors held for k frames in one launch ----------------
+ * What `for _ in range(k): env.step(actions)` computes around the reference with the rewards summed (the usual action
+ * repeat of frame-rate games), per game exactly k calls of pz_step on the same act_p1 / act_p2: frame 0 as pz_step runs
+ * it (cfg->auto_reset as configured, so a game that ended in the previous launch is reset in place right before it),
+ * frames 1 .. k-1 with auto_reset off -- a game that ends in frame j is frozen for frames j+1 .. k-1 (untouched state,
+ * reward 0, nothing counted) and is reset, if cfg->auto_reset, at the start of the NEXT launch.  Outputs:
+ *   state, obs_p1 / obs_p2   after the last frame (a game that ended early: its terminal frame);
+ *   terminated               game over after the launch;
+ *   rew_p1 / rew_p2          the SUM over the k frames of the frame's reward behind the fused reward pipeline (applied
+ *                            every frame): int32 exactly, float32 accumulated in frame order starting from +0.0f;
+ *   episode_stats            updated every frame, as k calls of pz_step would (lengths count frames);
+ *   episodes_done            (int64[1], device, may be NULL) += games that terminated: at most once per game and launch.
+ * An out-of-range action is counted into cfg->action_faults once per launch.  Every cfg->action_format and observation
+ * format is taken as by pz_step (a 2-byte tensor holds an even number of rows; no n % 8 rule: one frame's rows are
+ * written).  k < 1: PZ_E_CONFIG.  k == 1 computes what pz_step computes, on this entry point's own kernels (one wave
+ * per 64 games at every batch size): a per-frame caller is faster on pz_step / pz_step_bound. */
+int pz_step_held(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
+                 const void *act_p1, const void *act_p2, int32_t k,
                  int32_t *obs_p1, int32_t *obs_p2, void *rew_p1, void *rew_p2,
                  uint8_t *terminated, void *episode_stats, int64_t *episodes_done,
                  const pz_flight_tables *tables, void *stream);

@@ -2208,6 +2208,109 @@ __global__ __launch_bounds__(256) void render_kernel(const int32_t* __restrict__
     out[2] = r2;
 }
 
+// ---- frame skip: one pair of actions held for k frames (pz_step_held) -----------------------------------------------
+// Per game exactly k single-frame steps with the same two actions: frame 0 as pz_step runs it (cfg.auto_reset as
+// configured), frames 1 .. k-1 with auto_reset off -- a game that ends inside the launch stays frozen at its terminal
+// frame (the frozen path of frame_head: untouched state, reward 0, nothing counted) and is reset, if at all, by the
+// NEXT launch's first frame.  Rewards are summed over the frames behind the fused reward pipeline (int32 exactly,
+// float32 in frame order from +0.0f); the episode statistics are updated every frame; everything else -- state,
+// observations, `terminated` -- leaves once, after the last frame.
+// One wave per 64 games at every batch size, the frame loop of step_kernel's kRandom mode with the policy draw taken
+// out: actions loaded once under the state loads, the state in registers for k frames, frame_head of frame s + 1
+// behind frame s's tail, a human player's boldness draw deferred to the end of the launch (BoldDefer), the reward
+// table parked in VGPRs, the plain write-back behind an opaque pitch (see step_kernel for each of these).  A computer
+// player looks its flights up when the tables are passed and computes them in this wave when not (kNoScout).
+template <bool AI1, bool AI2, bool PACKED>
+__global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(1, 8)))
+void hold_kernel(PZ_HOT_PARAMS, const StepArgs a)
+{
+    const HotArgs hot{state, n, stride, act_p1, act_p2, act_format};
+    __shared__ __attribute__((aligned(16))) int32_t lds_obs[2][kLanes * PZ_OBS_DIM];
+
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t i = (int64_t)blockIdx.x * kLanes + lane;
+    const bool live = i < hot.n;
+    const uint32_t n32 = (uint32_t)hot.n;
+
+    // descriptors are built from kernel arguments only, so they are provably wave-uniform
+    const StateIO io{make_rsrc(hot.state, PACKED ? 0u : (uint32_t)(hot.stride * (PZ_STATE_WORDS * 4))),
+                     (uint32_t)hot.stride * 4u, (uint32_t)i * 4u};
+    const PackedIO pio = make_packed_io(hot.state, PACKED ? hot.stride : 0, i);
+    const bool as_float = a.cfg.ballpos_reward != 0 || a.cfg.normal_state_mode != 0;
+    const bool with_stats = a.episode_stats != nullptr && a.cfg.episode_stats_mode != 0;  // uniform
+    const StatsIO sio = make_stats_io(a.episode_stats, with_stats, a.stride, i);
+
+    Game g{};
+    RngId id = make_rng_id(a.cfg, live ? i : 0);
+    id.ks = make_parked_schedule(a.cfg.seed);  // the frame loop's key schedule lives in VGPRs (see KeySchedule)
+    const FlightLut lut = make_lut(a.tables);
+    int a1 = 0, a2 = 0;
+    uint32_t act_high = 0u;
+    load_actions(hot.act_p1, hot.act_p2, n32, (uint32_t)i, hot.act_format, a1, a2, act_high);
+    EpisodeStats st{0.0, 0.0, 0};
+    PackedWords was{};
+    if (live) {
+        if constexpr (PACKED)
+            was = load_game_packed(g, pio, true);
+        else
+            load_game(g, io);
+        if (with_stats) sio.load(st);
+    }
+
+    // what the frames behind the first run on: nothing is reset inside the launch.  The first frame's TAIL reads it
+    // too: a game that ends there freezes at frame 1 whatever cfg.auto_reset says, so the landing point after its last
+    // collision is observable (frame_tail: ex_observable)
+    pz_config held = a.cfg;
+    held.auto_reset = 0;
+    constexpr bool kDefer1 = !AI1, kDefer2 = !AI2;
+    BoldDefer bold{false, false, 0u, 0u};
+    const ZoneTable zones = park_zone_table(a.cfg);
+    const ScoutLink link{nullptr, nullptr, nullptr};
+    const bool resets = live && g.e.game_ended != 0 && a.cfg.auto_reset != 0;  // frame 0 resets this game in place
+    unsigned int finished = 0;  // at most 1: a game that ended stays frozen for the rest of the launch
+    int sum_i1 = 0;
+    float sum_f1 = 0.0f, sum_f2 = 0.0f;
+    // lds_obs[0] doubles as the wave's cooperative scratch (power-hit candidates without the table) until the
+    // observations are staged
+    FrameHead head = frame_head<AI1, AI2, kNoScout, kDefer1, kDefer2>(g, a.cfg, id, live, lane, lut, link, &bold);
+    for (int32_t s = 0; s < a.k; ++s) {
+        const bool last_frame = s == a.k - 1;
+        const bool frozen = head.frozen;
+        const int reward = frame_tail<AI1, AI2, kNoScout, false>(g, held, id, a1, a2, live, head, lds_obs[0], lane, lut, link,
+                                                                 nullptr, last_frame);
+        finished += (unsigned int)(live && g.e.game_ended && !frozen);
+        const Rewards rw = shape_rewards(held, g, reward, frozen, &zones);
+        if (with_stats) stats_update(st, held, rw, resets && s == 0, live && !frozen, as_float);
+        sum_i1 += rw.i1;
+        sum_f1 += rw.f1;
+        sum_f2 += rw.f2;
+        if (!last_frame) head = frame_head<AI1, AI2, kNoScout, kDefer1, kDefer2>(g, held, id, live, lane, lut, link, &bold);
+    }
+    // the launch's last recorded boldness draws (physics.py:218)
+    if (kDefer1 && bold.pending1) g.p1.bold = rng_integers(id, bold.counter1, 5u);
+    if (kDefer2 && bold.pending2) g.p2.bold = rng_integers(id, bold.counter2, 5u);
+
+    if (live) {
+        if constexpr (PACKED) {
+            store_game_packed(g, pio, was, true);
+        } else {
+            StateIO back = io;  // (column offsets computed afresh behind the frame loop: see step_kernel)
+            asm volatile("" : "+s"(back.pitch));
+            store_game(g, back);
+        }
+        if (with_stats) sio.store(st);
+    }
+    emit_outputs(a, g, Rewards{sum_i1, -sum_i1, sum_f1, sum_f2}, as_float, live, i, lane, 0, lds_obs);
+
+    count_action_faults(a.cfg, live && actions_out_of_range(a.cfg, a1, a2, act_high));  // once per launch
+    if (a.episodes_done != nullptr) {
+        // one atomic per wave: reduce the per-lane counts across the wavefront first
+        unsigned int total = finished;
+        for (int off = kLanes / 2; off > 0; off >>= 1) total += __shfl_down(total, off, kLanes);
+        if (lane == 0 && total != 0) atomicAdd(a.episodes_done, (unsigned long long)total);
+    }
+}
+
 
 // ---- host side ---------------------------------------------------------------------------------
 // Buffer descriptors address with 32-bit byte offsets: one launch handles at most this many games
@@ -2294,6 +2397,28 @@ static int launch_step(int mode, const StepArgs& a, hipStream_t stream)
     if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
     const dim3 grid(blocks_for(a.n, kLanes)), block(s.family == kStepKernel && s.scout == kNoScout ? kLanes : 2 * kLanes);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, PZ_HOT_ARGS(a), a);
+    return (int)hipGetLastError();
+}
+
+// pz_step_held: its own kernel family, chosen by who plays and by the state format alone (one wave per 64 games at
+// every batch size).  A diagnostic subset build (dev_keep) leaves the family out.
+template <int CODE>
+constexpr StepKernelFn held_kernel()
+{
+    if constexpr (diag::kSubset != 0u)
+        return nullptr;
+    else
+        return hold_kernel<(CODE & 4) != 0, (CODE & 2) != 0, (CODE & 1) != 0>;
+}
+constexpr StepKernelFn kHoldKernels[8] = {held_kernel<0>(), held_kernel<1>(), held_kernel<2>(), held_kernel<3>(),
+                                          held_kernel<4>(), held_kernel<5>(), held_kernel<6>(), held_kernel<7>()};
+
+static int launch_held(const StepArgs& a, hipStream_t stream)
+{
+    const StepKernelFn kernel =
+        kHoldKernels[(a.cfg.p1_computer != 0 ? 4 : 0) | (a.cfg.p2_computer != 0 ? 2 : 0) | (is_packed(a.cfg) ? 1 : 0)];
+    if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, kLanes)), dim3(kLanes), 0, stream, PZ_HOT_ARGS(a), a);
     return (int)hipGetLastError();
 }
 
@@ -2557,6 +2682,23 @@ int pz_step_many(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg
                rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
                *cfg};
     return launch_step(kTape, a, (hipStream_t)stream);
+}
+
+int pz_step_held(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, const void* act_p1,
+                 const void* act_p2, int32_t k, int32_t* obs_p1, int32_t* obs_p2, void* rew_p1, void* rew_p2,
+                 uint8_t* terminated, void* episode_stats, int64_t* episodes_done, const pz_flight_tables* tables,
+                 void* stream)
+{
+    if (int e = check_common(state, n, stride, cfg)) return e;
+    if (!act_p1 || !act_p2 || !obs_p1 || !obs_p2 || !rew_p1 || !rew_p2 || !terminated) return PZ_E_NULL;
+    if (k < 1) return PZ_E_CONFIG;
+    if (misaligned16(obs_p1) || misaligned16(obs_p2)) return PZ_E_ALIGN;
+    if (tables_misaligned(tables)) return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    StepArgs a{state,  n,          stride,        act_p1, act_p2, 0, 0, k, nullptr, obs_p1, obs_p2, rew_p1,
+               rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
+               *cfg};
+    return launch_held(a, (hipStream_t)stream);
 }
 
 int pz_random_actions(int32_t* act_p1, int32_t* act_p2, int64_t n, int64_t env_id_base, uint64_t action_seed,

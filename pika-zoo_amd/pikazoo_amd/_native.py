@@ -81,6 +81,9 @@ _SIGNATURES = {
     "pz_step_bound_bytes": (C.c_int64, []),
     "pz_step_bind": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, _P, _P, _P, _P, _P, _P]),
     "pz_step_bound": (C.c_int, [_P, _P, _P, _P]),
+    # (frame skip: pz_step's arguments + k behind the actions + episodes_done behind episode_stats)
+    "pz_step_held": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                               _P, _P]),
     "pz_count_packed_misfits": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
     "pz_probe_write": (C.c_int, [_P, _P, C.c_int64, _P]),
     "pz_probe_frame_bytes": (C.c_int64, []),

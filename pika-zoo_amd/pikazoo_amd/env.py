@@ -182,6 +182,15 @@ class raw_env(ParallelEnv):
     the punch effect is drawn too: its two ball attributes are tracked after every ``step()``, a k-frame
     launch clears it; off by default, which keeps ``render()`` free of side effects and ``step()`` a single launch).
 
+    ``frame_skip`` (k >= 1, default 1: action repeat.  One ``step(actions)`` holds the two actions for k frames in ONE
+    launch (``pz_step_held``): per game exactly k single-frame steps with the same actions, the first with ``auto_reset``
+    as configured, the rest without -- a game that ends inside the repeat stays at its terminal frame and is reset, with
+    ``auto_reset``, right before the next ``step``.  Rewards are the sum of the k frames' (fully wrapped) rewards,
+    observations / terminations / state those after the last frame, a fused ``RecordEpisodeStatistics`` counts every
+    frame; ``steps_done`` counts ``step`` calls.  It sits OUTSIDE every fused wrapper; a wrapper that would run outside
+    the kernel on the step's outputs would see one frame in k and is refused (ValueError), and so are ``step_random``,
+    ``rollout_random`` and ``step_many``, whose k is a frame count of its own).
+
     ``output_ring`` (k >= 1 rotating sets of the observation / reward / termination buffers: the reference returns
     FRESH arrays from every ``step`` (pikazoo_env.py:215-235), this env returns views of env-owned buffers -- with
     the default ring of 1 the next ``step`` overwrites them, with ``output_ring=k`` the results of the last k
@@ -203,7 +212,7 @@ class raw_env(ParallelEnv):
                  validate_actions: bool = True, scalar_api: bool = False, flight_tables=True,
                  sprite_dir=None, sprites=None, state_format: str = "int32", scenery: bool = False,
                  observation_dtype=torch.int32, output_ring: int = 1, place_trajectories: bool = True,
-                 validate_every: int = 64):
+                 validate_every: int = 64, frame_skip: int = 1):
         assert serve in ("winner", "alternate", "random")  # pikazoo_env.py:104
         if render_mode not in (None, "rgb_array"):
             raise NotImplementedError('render_mode must be None or "rgb_array" (no "human" window on a GPU batch)')
@@ -225,6 +234,8 @@ class raw_env(ParallelEnv):
             raise ValueError("the packed state format holds scores up to 32767")
         if int(output_ring) < 1:
             raise ValueError("output_ring must be >= 1")
+        if isinstance(frame_skip, bool) or int(frame_skip) != frame_skip or int(frame_skip) < 1:
+            raise ValueError(f"frame_skip must be an integer >= 1 (the frames one step() holds its actions for), got {frame_skip!r}")
         if not isinstance(flight_tables, (bool, str, type(None))) or flight_tables not in _TABLE_MODES:
             raise ValueError('flight_tables must be True / "both", "power_hit" or False / "none"')
         self._lib = _native.load()  # raises when the HIP library has not been built
@@ -256,6 +267,7 @@ class raw_env(ParallelEnv):
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
         self.state_format = state_format
+        self.frame_skip = int(frame_skip)
 
         cfg = _native.PzConfig()
         cfg.winning_score = self.winning_score
@@ -489,6 +501,13 @@ class raw_env(ParallelEnv):
     # constructed later sits in the reference's stack.  Once one reward wrapper works that way, every later wrapper that
     # reads rewards must too (`_unfused_reward`).
     def _note_unfused(self, name: str, reward: bool = False):
+        if self.frame_skip > 1 and name != "SimplifyAction":
+            # (a second SimplifyAction only maps the ACTIONS on their way in, once per step() like the held actions
+            # themselves: k frames of the mapped action are the mapped action held for k frames)
+            raise ValueError(f"{name} cannot be fused at this place of the wrapper stack and would run on the outputs of "
+                             f"step(), which with frame_skip={self.frame_skip} show one frame in {self.frame_skip}: its "
+                             "per-frame rewards / statistics would differ from the reference's.  Use a stack the kernel "
+                             "fuses, or frame_skip=1")
         self._unfused.append(name)
         self._unfused_reward = self._unfused_reward or reward
 
@@ -734,7 +753,7 @@ class raw_env(ParallelEnv):
         return a
 
     def step(self, actions: Dict[str, torch.Tensor]):
-        """One frame of every game.  ``actions[agent]``: int tensor ``[num_envs]`` in
+        """One frame of every game (``frame_skip`` frames with the actions held, rewards summed).  ``actions[agent]``: int tensor ``[num_envs]`` in
         ``[0, action_space(agent).n)`` (ints / arrays are accepted for small batches).  As in the
         reference, both agents' key states are read even for a computer-controlled side."""
         if not self.agents:
@@ -777,18 +796,21 @@ class raw_env(ParallelEnv):
             self._next_outputs()
         self._last_traj = None  # (this launch overwrites the single-frame buffers)
         out = self._out
-        # pz_step through its prepared-argument form: one FFI call with four scalars (the twelve buffers and the
-        # configuration were bound once) -- the host side of a step stays below the duration of the launch it issues
-        bound = out.bound[f1] if out.bound_key[f1] == self._cfg_version else self._bound_step(f1)
-        if _get_device() == self._dev_index:
-            rc = self._step_bound(bound, p1, p2, _raw_stream(self._dev_index))
+        if self.frame_skip > 1:
+            self._step_held(out, p1, p2, f1)
         else:
-            with torch.cuda.device(self.device):
-                rc = self._lib.pz_step_bound(bound, p1, p2, self._stream())
-        if rc:
-            _native.check(rc, "pz_step")
+            # pz_step through its prepared-argument form: one FFI call with four scalars (the twelve buffers and the
+            # configuration were bound once) -- the host side of a step stays below the duration of the launch it issues
+            bound = out.bound[f1] if out.bound_key[f1] == self._cfg_version else self._bound_step(f1)
+            if _get_device() == self._dev_index:
+                rc = self._step_bound(bound, p1, p2, _raw_stream(self._dev_index))
+            else:
+                with torch.cuda.device(self.device):
+                    rc = self._lib.pz_step_bound(bound, p1, p2, self._stream())
+            if rc:
+                _native.check(rc, "pz_step")
         if self._scenery is not None:
-            self._track_scenery()
+            self._track_scenery(resync=self.frame_skip > 1)  # (a k-frame launch: its inner frames cannot be seen)
         self.steps_done += 1
         if self._faults is not None:  # validate_actions: the launch counted out-of-range actions (pikazoo_env.py:182)
             self._since_poll += 1
@@ -802,6 +824,26 @@ class raw_env(ParallelEnv):
         if out.result is None or out.result_key != self._cfg_version:
             out.result, out.result_key = self._pack_step(), self._cfg_version
         return out.result
+
+    def _step_held(self, out, p1, p2, fmt):
+        """``frame_skip`` > 1: the two action vectors held for k frames in one launch (``pz_step_held``)."""
+        p = out.ptrs
+        self._cfg.action_format = fmt  # (the launch copies the configuration; every other call takes int32)
+        try:
+            with torch.cuda.device(self.device):
+                rc = self._lib.pz_step_held(p[0], self.num_envs, self._stride, self._cfg_ref, p1, p2, self.frame_skip, p[1],
+                                            p[2], p[3], p[4], p[5], self._stats_ptr(), self._episodes.data_ptr(),
+                                            self._tables_ref, self._stream())
+        finally:
+            self._cfg.action_format = 0
+        if rc:
+            _native.check(rc, "pz_step_held")
+
+    def _no_frame_skip(self, what: str):
+        if self.frame_skip > 1:
+            raise ValueError(f"{what} runs its own k frames per launch with a new action every frame; this env holds every "
+                             f"action for frame_skip={self.frame_skip} frames, which only step() does: use step(), or an env "
+                             "with frame_skip=1")
 
     # ---- out-of-range actions (validate_actions) -------------------------------------------------------------------
     def _raise_action_fault(self):
@@ -838,6 +880,7 @@ class raw_env(ParallelEnv):
         """``k`` frames under the uniform random policy drawn on device (Philox stream
         ``action_seed``, step indices ``t0 .. t0+k-1``; ``t0`` defaults to ``steps_done``) in ONE
         launch.  Returns the last frame's step tuple."""
+        self._no_frame_skip("step_random")
         self._no_unfused_wrappers("step_random")
         if t0 is None:
             t0 = self.steps_done
@@ -863,6 +906,7 @@ class raw_env(ParallelEnv):
         ``{agent: int32[k, N, 35]}``, ``rewards`` ``{agent: [k, N]}``, ``terminations``
         ``bool[k, N]``.  Bit-identical to ``k`` calls of ``step(random_actions(...))``; the state
         tensor is read and written once.  Pass the previous result as ``out`` to reuse its buffers."""
+        self._no_frame_skip("rollout_random")
         self._no_unfused_wrappers("rollout_random")
         if t0 is None:
             t0 = self.steps_done
@@ -895,6 +939,7 @@ class raw_env(ParallelEnv):
         ``IndexError`` from the NEXT call that polls (the next ``step_many`` / a later ``step``) -- a caller whose last
         call this is asks with :meth:`check_actions` before it trusts the trajectory; with ``validate_every=1`` (strict)
         this call synchronises and raises itself."""
+        self._no_frame_skip("step_many")
         self._no_unfused_wrappers("step_many")
         n, dev = self.num_envs, self.device
         if actions.dim() != 3 or actions.shape[1] != 2 or actions.shape[2] != n:
@@ -1016,6 +1061,7 @@ class raw_env(ParallelEnv):
         # normalized or not: the row dtype (int32 / int16 / float16 / bfloat16) does not change the trajectory
         d["normalize_obs"] = int(self._cfg.normalize_obs in (1, 5, 6))
         d["additional_reward"] = [float(v) for v in self._cfg.additional_reward]
+        d["frame_skip"] = self.frame_skip
         return d
 
     def state_dict(self):
@@ -1036,11 +1082,14 @@ class raw_env(ParallelEnv):
         cfg = sd.get("config")
         if cfg is not None:
             mine = self._cfg_dict()
+            cfg = {"frame_skip": 1, **cfg}  # (a checkpoint from before frame_skip existed: every step was one frame)
             diff = {k: (cfg.get(k), mine[k]) for k in mine if cfg.get(k) != mine[k]}
             if diff:
                 raise ValueError(f"checkpoint was taken with another configuration (saved, this env): {diff}")
         elif int(sd.get("seed", self.seed)) != self.seed or int(sd.get("env_id_base", self.env_id_base)) != self.env_id_base:
             raise ValueError("checkpoint was taken with another seed / env_id_base")
+        elif self.frame_skip != 1:
+            raise ValueError(f"checkpoint was taken with frame_skip=1 (it names none), this env has frame_skip={self.frame_skip}")
         stats = sd.get("episode_stats")
         if (stats is None) != (self._stats is None):
             raise ValueError("checkpoint and env disagree on RecordEpisodeStatistics")
