@@ -21,7 +21,8 @@ def main():
     # same kwargs as the reference's pikazoo_v0.env(...) + the batched ones
     env = pikazoo_v0.env(winning_score=15, serve="winner", is_player2_computer=True,
                          num_envs=n, device="cuda:0", seed=0, validate_actions=False)
-    # (frame_skip=4 in the line above: the usual action repeat -- every step() then holds its actions for 4 frames)
+    # (frame_skip=4 in the line above: the usual action repeat -- every step() then holds its actions for 4 frames, and
+    # raw.rollout_random_held(action_seed=1, k=32) below collects 32 such policy steps per launch)
     env = RecordEpisodeStatistics(NormalizeObservation(SimplifyAction(env)))  # fused into the step kernel
     obs, infos = env.reset()
     print("agents:", env.agents, "| obs", tuple(obs["player_1"].shape), obs["player_1"].dtype,

@@ -342,6 +342,34 @@ int pz_step_held(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg
                  uint8_t *terminated, void *episode_stats, int64_t *episodes_done,
                  const pz_flight_tables *tables, void *stream);
 
+/* ---- frame skip over a trajectory: k policy steps, each held for `hold` frames, in one launch ----
+ * pz_step_many_held is per game exactly k calls of pz_step_held(..., actions[t][0], actions[t][1], hold, ...), t = 0 ..
+ * k-1, the t-th call's outputs written to slab t of the [k][n]... tensors laid out as pz_step_many lays them out; the
+ * state is read once and written once.  pz_rollout_random_held is the same with the actions of policy step t drawn as
+ * pz_random_actions(..., action_seed, t0 + t, n_actions) draws them -- one draw per POLICY STEP, not per frame -- and
+ * written to actions[t] (int32[k][2][n], may be NULL).  Per game:
+ *   frame 0 of every policy step runs with cfg->auto_reset as configured, frames 1 .. hold-1 with it off: a game that
+ *   ends inside a repeat is frozen for the rest of it and, with auto_reset, reset in place right before frame 0 of the
+ *   next policy step INSIDE the launch (a game can end several times per launch; episodes_done grows by one for each);
+ *   without auto_reset it stays frozen to the end of the launch (reward 0, its terminal observation, terminated = 1 in
+ *   every later slab);
+ *   slab t holds the observations and `terminated` after the last frame of policy step t and the rewards summed over
+ *   its `hold` frames behind the fused reward pipeline (int32 exactly; float32 in frame order from +0.0f, afresh every
+ *   policy step); episode_stats are updated every frame.
+ * hold == 1 computes what pz_step_many / pz_rollout_random compute.  k < 1 or hold < 1: PZ_E_SIZE.  The tape is int32
+ * alone (cfg->action_format = PZ_ACT_I32, else PZ_E_CONFIG); an out-of-range action on it is counted into
+ * cfg->action_faults as pz_step_many counts it.  n must be a multiple of 4 when k > 1 (of 8 for 2-byte rows). */
+int pz_step_many_held(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
+                      const void *actions, int32_t k, int32_t hold,
+                      int32_t *obs_p1, int32_t *obs_p2, void *rew_p1, void *rew_p2,
+                      uint8_t *terminated, void *episode_stats, int64_t *episodes_done,
+                      const pz_flight_tables *tables, void *stream);
+int pz_rollout_random_held(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
+                           uint64_t action_seed, uint64_t t0, int32_t k, int32_t hold, int32_t *actions,
+                           int32_t *obs_p1, int32_t *obs_p2, void *rew_p1, void *rew_p2,
+                           uint8_t *terminated, void *episode_stats, int64_t *episodes_done,
+                           const pz_flight_tables *tables, void *stream);
+
 /* ---- the policy stream alone (for hosts that want the actions in HBM) -------------------- */
 int pz_random_actions(int32_t *act_p1, int32_t *act_p2, int64_t n, int64_t env_id_base,
                       uint64_t action_seed, uint64_t t, int32_t n_actions, void *stream);

@@ -2311,6 +2311,154 @@ void hold_kernel(PZ_HOT_PARAMS, const StepArgs a)
     }
 }
 
+// ---- frame skip over a trajectory: k policy steps, each held for `hold` frames (pz_step_many_held, -----------------
+// ---- pz_rollout_random_held) ---------------------------------------------------------------------------------------
+// Per game exactly k launches of hold_kernel, the t-th one's outputs written to slab t of the [k][n]... tensors: the
+// trajectory loop of step_kernel's kRollout / kTape modes around hold_kernel's frame loop.  The state is read once and
+// written once; a game that ends inside a repeat stays frozen for the rest of it and -- with cfg.auto_reset -- is reset
+// in place by the head of the NEXT policy step's frame 0, inside the launch (a game can end several times per launch).
+// The two configurations are hold_kernel's: a.cfg for the head of a policy step's frame 0, the auto_reset = 0 copy for
+// every other head and for every tail (a game that ends in any frame of a repeat freezes or is reset by a later head;
+// either way the landing point after its last collision is evaluated, frame_tail: ex_observable).
+// a.k counts policy steps (tape rows, policy draws, slabs); the rewards of a slab are summed afresh from 0 / +0.0f.
+// The outputs leave as in the kRollout loop: slab t staged, the head of policy step t + 1 (its gathers) issued, then
+// the row stores.  A frame inside a repeat stores no rows; behind its head the same number of dropped stores is issued
+// so that the tail's wait for the gathers is vmcnt(rows) on every path into it (see step_kernel's frame loop) and the
+// frame behind a slab does not drain that slab's stores.
+// A human player's boldness draw stays deferred to the end of the launch: the boldness is state, not observation.
+// One wave per 64 games at every batch size; a computer player looks its flights up when the tables are passed and
+// computes them in this wave when not (kNoScout).  MODE: kRollout / kTape.
+// The slab staging (TrajOut: 72 registers of row pieces in flight) and the parked key schedules put the family at
+// 186-275 VGPRs, one or two waves per SIMD where hold_kernel's 125-160 allow three: at 65 536 games (one wave per SIMD
+// to place) that costs nothing, at 524 288 the frames inside a repeat are bound by VALU issue and it does.
+template <bool AI1, bool AI2, int MODE, bool PACKED, bool OBS16>
+__global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(1, 8)))
+void held_traj_kernel(PZ_HOT_PARAMS, const StepArgs a, const int32_t hold)
+{
+    static_assert(MODE == kRollout || MODE == kTape, "the trajectory launches");
+    const HotArgs hot{state, n, stride, act_p1, act_p2, act_format};
+    __shared__ __attribute__((aligned(16))) int32_t lds_obs[2][kLanes * PZ_OBS_DIM];
+    __shared__ int32_t tape_lds[MODE == kTape ? kTapeWords : 1];  // parked action tape (kTape only)
+
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t i = (int64_t)blockIdx.x * kLanes + lane;
+    const bool live = i < hot.n;
+    const uint32_t n32 = (uint32_t)hot.n;
+
+    // descriptors are built from kernel arguments only, so they are provably wave-uniform
+    const StateIO io{make_rsrc(hot.state, PACKED ? 0u : (uint32_t)(hot.stride * (PZ_STATE_WORDS * 4))),
+                     (uint32_t)hot.stride * 4u, (uint32_t)i * 4u};
+    const PackedIO pio = make_packed_io(hot.state, PACKED ? hot.stride : 0, i);
+    const bool as_float = a.cfg.ballpos_reward != 0 || a.cfg.normal_state_mode != 0;
+    const bool with_stats = a.episode_stats != nullptr && a.cfg.episode_stats_mode != 0;  // uniform
+    const StatsIO sio = make_stats_io(a.episode_stats, with_stats, a.stride, i);
+
+    Game g{};
+    RngId id = make_rng_id(a.cfg, live ? i : 0);
+    id.ks = make_parked_schedule(a.cfg.seed);  // the frame loop's key schedules live in VGPRs (see KeySchedule)
+    KeySchedule policy = make_rolling_key(a.action_seed);
+    if (MODE == kRollout) policy = make_parked_schedule(a.action_seed);
+    const FlightLut lut = make_lut(a.tables);
+    EpisodeStats st{0.0, 0.0, 0};
+    PackedWords was{};
+    if (live) {
+        if constexpr (PACKED)
+            was = load_game_packed(g, pio, true);
+        else
+            load_game(g, io);
+        if (with_stats) sio.load(st);
+    }
+    // the tape: one parked row per POLICY STEP, kTapeChunk policy steps per fetch, the first behind the state loads
+    unsigned char* const parked = reinterpret_cast<unsigned char*>(tape_lds);
+    bool bad_action = false;
+    auto fetch_tape_chunk = [&](int32_t s0, auto first) {
+        bad_action |= park_tape_chunk<decltype(first)::value, true, true>(static_cast<const int32_t*>(a.act_p1), a.n, n32, a.k, s0,
+                                                                          io.voff, parked, lane, action_count(a.cfg));
+        wave_lds_handover<true>();  // every lane reads back its own bytes only
+    };
+    if (MODE == kTape) fetch_tape_chunk(0, std::true_type{});
+
+    pz_config held = a.cfg;  // every frame's tail and the heads inside a repeat: nothing is reset there
+    held.auto_reset = 0;
+    const uint32_t n_actions = a.cfg.simplify_action ? 13u : 18u;
+    constexpr bool kDefer1 = !AI1, kDefer2 = !AI2;
+    BoldDefer bold{false, false, 0u, 0u};
+    const ZoneTable zones = park_zone_table(a.cfg);
+    const ScoutLink link{nullptr, nullptr, nullptr};
+    TrajOut<OBS16> out;
+    out.init(a, i, lane, live);
+    int a1 = 0, a2 = 0;
+    if (MODE == kRollout) policy_actions(id.id_lo, id.id_hi, policy, a.t0, n_actions, a1, a2);
+    unsigned int finished = 0;  // a game can end once per policy step
+    bool resets = live && g.e.game_ended != 0 && a.cfg.auto_reset != 0;  // the coming frame 0 resets this game in place
+    // every state load lands before the frame loop (see step_kernel)
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); expcnt / lgkmcnt untouched
+    // lds_obs[0] doubles as the wave's cooperative scratch (power-hit candidates without the table) until a slab's
+    // observations are staged
+    FrameHead head = frame_head<AI1, AI2, kNoScout, kDefer1, kDefer2>(g, a.cfg, id, live, lane, lut, link, &bold);
+    if (AI1 || AI2) issue_dropped_stores<TrajOut<OBS16>::kStores>();
+    for (int32_t t = 0; t < a.k; ++t) {
+        if (MODE == kTape) {
+            const int slot = t % kTapeChunk;
+            if (slot == 0 && t != 0) fetch_tape_chunk(t, std::false_type{});
+            a1 = parked[(slot * 2 + 0) * kLanes + lane];
+            a2 = parked[(slot * 2 + 1) * kLanes + lane];
+        }
+        int sum_i1 = 0;
+        float sum_f1 = 0.0f, sum_f2 = 0.0f;
+        for (int32_t j = 0; j < hold; ++j) {
+            // the launch's last frame, not a slab's: `last_frame` only decides whether the landing point after a collision
+            // is evaluated for the state written back (frame_tail: ex_observable), and no observation row carries it
+            const bool last_frame = t == a.k - 1 && j == hold - 1;
+            const bool frozen = head.frozen;
+            const int reward = frame_tail<AI1, AI2, kNoScout, false>(g, held, id, a1, a2, live, head, lds_obs[0], lane, lut,
+                                                                     link, nullptr, last_frame);
+            finished += (unsigned int)(live && g.e.game_ended && !frozen);
+            const Rewards rw = shape_rewards(held, g, reward, frozen, &zones);
+            if (with_stats) stats_update(st, held, rw, resets && j == 0, live && !frozen, as_float);
+            sum_i1 += rw.i1;
+            sum_f1 += rw.f1;
+            sum_f2 += rw.f2;
+            if (j + 1 < hold) {
+                head = frame_head<AI1, AI2, kNoScout, kDefer1, kDefer2>(g, held, id, live, lane, lut, link, &bold);
+                if (AI1 || AI2) issue_dropped_stores<TrajOut<OBS16>::kStores>();
+            }
+        }
+        out.template stage<traj_small_aux(AI1 || AI2)>(a, g, Rewards{sum_i1, -sum_i1, sum_f1, sum_f2}, as_float, live, a1, a2,
+                                                       MODE == kRollout && a.act_out != nullptr, lane, lds_obs);
+        if (t + 1 < a.k) {  // this policy step's outputs are staged: the game may move on (and be reset)
+            resets = live && g.e.game_ended != 0 && a.cfg.auto_reset != 0;
+            head = frame_head<AI1, AI2, kNoScout, kDefer1, kDefer2>(g, a.cfg, id, live, lane, lut, link, &bold);
+        }
+        // the next policy step's draw (one block too many per launch) runs under the LDS reads of this slab's rows
+        out.flush(lds_obs, lane, [&]() {
+            if (MODE == kRollout) policy_actions(id.id_lo, id.id_hi, policy, a.t0 + (uint64_t)t + 1u, n_actions, a1, a2);
+        });
+        out.advance();
+    }
+    // the launch's last recorded boldness draws (physics.py:218)
+    if (kDefer1 && bold.pending1) g.p1.bold = rng_integers(id, bold.counter1, 5u);
+    if (kDefer2 && bold.pending2) g.p2.bold = rng_integers(id, bold.counter2, 5u);
+
+    if (live) {
+        if constexpr (PACKED) {
+            store_game_packed(g, pio, was, true);
+        } else {
+            StateIO back = io;  // (column offsets computed afresh behind the frame loop: see step_kernel)
+            asm volatile("" : "+s"(back.pitch));
+            store_game(g, back);
+        }
+        if (with_stats) sio.store(st);
+    }
+    if (MODE == kTape) count_action_faults(a.cfg, live && bad_action);
+    if (a.episodes_done != nullptr) {
+        // one atomic per wave: reduce the per-lane counts across the wavefront first
+        unsigned int total = finished;
+        for (int off = kLanes / 2; off > 0; off >>= 1) total += __shfl_down(total, off, kLanes);
+        if (lane == 0 && total != 0) atomicAdd(a.episodes_done, (unsigned long long)total);
+    }
+}
+
 
 // ---- host side ---------------------------------------------------------------------------------
 // Buffer descriptors address with 32-bit byte offsets: one launch handles at most this many games
@@ -2419,6 +2567,39 @@ static int launch_held(const StepArgs& a, hipStream_t stream)
         kHoldKernels[(a.cfg.p1_computer != 0 ? 4 : 0) | (a.cfg.p2_computer != 0 ? 2 : 0) | (is_packed(a.cfg) ? 1 : 0)];
     if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
     hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, kLanes)), dim3(kLanes), 0, stream, PZ_HOT_ARGS(a), a);
+    return (int)hipGetLastError();
+}
+
+// pz_step_many_held / pz_rollout_random_held: their own family too, chosen by who plays, the launch mode, the state
+// format and the row width (compile-time in a trajectory launch, see TrajOut::flush) -- 32 kernels, every one reachable.
+// bits of the code: 16 player 1 = computer, 8 player 2, 4 the tape, 2 the packed state, 1 2-byte rows.
+using HeldTrajFn = void (*)(PZ_HOT_PARAMS, const StepArgs, const int32_t);
+constexpr int held_traj_code(bool ai1, bool ai2, int mode, bool packed, bool obs16)
+{
+    return (ai1 ? 16 : 0) | (ai2 ? 8 : 0) | (mode == kTape ? 4 : 0) | (packed ? 2 : 0) | (obs16 ? 1 : 0);
+}
+template <int CODE>
+constexpr HeldTrajFn held_traj()
+{
+    if constexpr (diag::kSubset != 0u)
+        return nullptr;
+    else
+        return held_traj_kernel<(CODE & 16) != 0, (CODE & 8) != 0, (CODE & 4) != 0 ? kTape : kRollout, (CODE & 2) != 0,
+                                (CODE & 1) != 0>;
+}
+template <int... CODE>
+constexpr std::array<HeldTrajFn, sizeof...(CODE)> held_traj_table(std::integer_sequence<int, CODE...>)
+{
+    return {held_traj<CODE>()...};
+}
+constexpr auto kHeldTrajKernels = held_traj_table(std::make_integer_sequence<int, 32>());
+
+static int launch_held_traj(int mode, const StepArgs& a, int32_t hold, hipStream_t stream)
+{
+    const HeldTrajFn kernel = kHeldTrajKernels[held_traj_code(a.cfg.p1_computer != 0, a.cfg.p2_computer != 0, mode,
+                                                              is_packed(a.cfg), rows16(a.cfg.normalize_obs))];
+    if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, kLanes)), dim3(kLanes), 0, stream, PZ_HOT_ARGS(a), a, hold);
     return (int)hipGetLastError();
 }
 
@@ -2699,6 +2880,42 @@ int pz_step_held(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg
                rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
                *cfg};
     return launch_held(a, (hipStream_t)stream);
+}
+
+int pz_step_many_held(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, const void* actions, int32_t k,
+                      int32_t hold, int32_t* obs_p1, int32_t* obs_p2, void* rew_p1, void* rew_p2, uint8_t* terminated,
+                      void* episode_stats, int64_t* episodes_done, const pz_flight_tables* tables, void* stream)
+{
+    if (int e = check_common(state, n, stride, cfg)) return e;
+    if (!actions || !obs_p1 || !obs_p2 || !rew_p1 || !rew_p2 || !terminated) return PZ_E_NULL;
+    if (k < 1 || hold < 1) return PZ_E_SIZE;
+    if (cfg->action_format != PZ_ACT_I32) return PZ_E_CONFIG;  // the tape is parked from int32 rows, as pz_step_many's
+    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (rows16(cfg->normalize_obs) ? 7 : 3)) != 0))
+        return PZ_E_ALIGN;
+    if (tables_misaligned(tables)) return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    StepArgs a{state,  n,          stride,        actions, nullptr, 0, 0, k, nullptr, obs_p1, obs_p2, rew_p1,
+               rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
+               *cfg};
+    return launch_held_traj(kTape, a, hold, (hipStream_t)stream);
+}
+
+int pz_rollout_random_held(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, uint64_t action_seed,
+                           uint64_t t0, int32_t k, int32_t hold, int32_t* actions, int32_t* obs_p1, int32_t* obs_p2,
+                           void* rew_p1, void* rew_p2, uint8_t* terminated, void* episode_stats, int64_t* episodes_done,
+                           const pz_flight_tables* tables, void* stream)
+{
+    if (int e = check_common(state, n, stride, cfg)) return e;
+    if (!obs_p1 || !obs_p2 || !rew_p1 || !rew_p2 || !terminated) return PZ_E_NULL;
+    if (k < 1 || hold < 1) return PZ_E_SIZE;
+    if (misaligned16(obs_p1) || misaligned16(obs_p2) || (k > 1 && (n & (rows16(cfg->normalize_obs) ? 7 : 3)) != 0))
+        return PZ_E_ALIGN;
+    if (tables_misaligned(tables)) return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    StepArgs a{state,  n,          stride,        nullptr, nullptr, action_seed, t0, k, actions, obs_p1, obs_p2, rew_p1,
+               rew_p2, terminated, episode_stats, reinterpret_cast<unsigned long long*>(episodes_done), tables_of(tables),
+               *cfg};
+    return launch_held_traj(kRollout, a, hold, (hipStream_t)stream);
 }
 
 int pz_random_actions(int32_t* act_p1, int32_t* act_p2, int64_t n, int64_t env_id_base, uint64_t action_seed,

@@ -93,6 +93,11 @@ _SIGNATURES = {
                                     C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pz_step_many": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, C.c_int32, _P, _P, _P, _P, _P, _P,
                                _P, _P, _P]),
+    # (the k-step trajectory launches of a frame-skip env: `hold` behind k)
+    "pz_step_many_held": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, C.c_int32, C.c_int32, _P, _P, _P, _P,
+                                    _P, _P, _P, _P, _P]),
+    "pz_rollout_random_held": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), C.c_uint64, C.c_uint64,
+                                         C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pz_random_actions": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, _P]),
     "pz_scenery_init": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P]),
     "pz_scenery_track": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(PzConfig), C.c_int32, _P]),

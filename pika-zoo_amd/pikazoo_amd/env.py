@@ -843,7 +843,7 @@ class raw_env(ParallelEnv):
         if self.frame_skip > 1:
             raise ValueError(f"{what} runs its own k frames per launch with a new action every frame; this env holds every "
                              f"action for frame_skip={self.frame_skip} frames, which only step() does: use step(), or an env "
-                             "with frame_skip=1")
+                             "with frame_skip=1 (rollout_random_held / step_many_held run k held policy steps per launch)")
 
     # ---- out-of-range actions (validate_actions) -------------------------------------------------------------------
     def _raise_action_fault(self):
@@ -907,23 +907,40 @@ class raw_env(ParallelEnv):
         ``bool[k, N]``.  Bit-identical to ``k`` calls of ``step(random_actions(...))``; the state
         tensor is read and written once.  Pass the previous result as ``out`` to reuse its buffers."""
         self._no_frame_skip("rollout_random")
-        self._no_unfused_wrappers("rollout_random")
+        return self._rollout_random("rollout_random", action_seed, k, t0, out)
+
+    def rollout_random_held(self, action_seed: int, k: int, t0: Optional[int] = None, out: Optional[dict] = None):
+        """``k`` POLICY STEPS under the random policy in ONE launch (``pz_rollout_random_held``), each draw held for
+        ``frame_skip`` frames, keeping every policy step's outputs: the result dict of :meth:`rollout_random` with k
+        slabs, bit-identical to ``k`` calls of ``step(random_actions(...))`` on this env -- rewards summed over the held
+        frames, a game that ended inside a repeat reset (``auto_reset``) before the next policy step inside the launch.
+        ``t0`` (default ``steps_done``) and ``steps_done`` count policy steps.  With ``frame_skip=1`` this is
+        :meth:`rollout_random`."""
+        return self._rollout_random("rollout_random_held", action_seed, k, t0, out)
+
+    def _rollout_random(self, what, action_seed, k, t0, out):
+        self._no_unfused_wrappers(what)
         if t0 is None:
             t0 = self.steps_done
         k, n, dev = int(k), self.num_envs, self.device
         if k < 1:
             raise ValueError("k must be >= 1")
         if k > 1 and n % self._traj_multiple() != 0:
-            raise ValueError(f"rollout_random needs num_envs to be a multiple of {self._traj_multiple()}")
+            raise ValueError(f"{what} needs num_envs to be a multiple of {self._traj_multiple()}")
         if out is None or out["_k"] != k:
             out = self._alloc_trajectory(k)
             out["actions"] = torch.empty((k, 2, n), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _native.check(self._lib.pz_rollout_random(
-                self._state_ptr, n, self._stride, self._cfg_ref, int(action_seed) & 0xFFFFFFFFFFFFFFFF, int(t0), k,
-                out["actions"].data_ptr(), out["_obs"][0].data_ptr(), out["_obs"][1].data_ptr(),
+        seed = int(action_seed) & 0xFFFFFFFFFFFFFFFF
+        tail = (out["actions"].data_ptr(), out["_obs"][0].data_ptr(), out["_obs"][1].data_ptr(),
                 out["_rew"][0].data_ptr(), out["_rew"][1].data_ptr(), out["_term"].data_ptr(),
-                self._stats_ptr(), self._episodes.data_ptr(), self._tables_ref, self._stream()), "pz_rollout_random")
+                self._stats_ptr(), self._episodes.data_ptr(), self._tables_ref, self._stream())
+        with torch.cuda.device(dev):
+            if self.frame_skip > 1:
+                _native.check(self._lib.pz_rollout_random_held(self._state_ptr, n, self._stride, self._cfg_ref, seed, int(t0),
+                                                               k, self.frame_skip, *tail), "pz_rollout_random_held")
+            else:
+                _native.check(self._lib.pz_rollout_random(self._state_ptr, n, self._stride, self._cfg_ref, seed, int(t0), k,
+                                                          *tail), "pz_rollout_random")
         if self._scenery is not None:
             self._track_scenery(resync=True)
         self.steps_done += k
@@ -940,7 +957,18 @@ class raw_env(ParallelEnv):
         call this is asks with :meth:`check_actions` before it trusts the trajectory; with ``validate_every=1`` (strict)
         this call synchronises and raises itself."""
         self._no_frame_skip("step_many")
-        self._no_unfused_wrappers("step_many")
+        return self._step_many("step_many", actions, out)
+
+    def step_many_held(self, actions: torch.Tensor, out: Optional[dict] = None):
+        """``k`` POLICY STEPS of GIVEN actions (``[k, 2, N]``: policy step, agent, game) in ONE launch
+        (``pz_step_many_held``), each pair of actions held for ``frame_skip`` frames, keeping every policy step's
+        outputs: the result dict of :meth:`step_many` with k slabs, bit-identical to ``k`` calls of :meth:`step` on the
+        ``k`` slices of this env.  Tape dtypes and ``validate_actions`` as in :meth:`step_many`; ``steps_done`` grows by
+        k.  With ``frame_skip=1`` this is :meth:`step_many`."""
+        return self._step_many("step_many_held", actions, out)
+
+    def _step_many(self, what, actions, out):
+        self._no_unfused_wrappers(what)
         n, dev = self.num_envs, self.device
         if actions.dim() != 3 or actions.shape[1] != 2 or actions.shape[2] != n:
             raise ValueError(f"actions must have shape [k, 2, {n}]")
@@ -956,16 +984,19 @@ class raw_env(ParallelEnv):
             actions = actions.to(device=dev, dtype=torch.int32).contiguous()  # (the smaller integer types: widened, exact)
         k = int(actions.shape[0])
         if k > 1 and n % self._traj_multiple() != 0:
-            raise ValueError(f"step_many needs num_envs to be a multiple of {self._traj_multiple()}")
+            raise ValueError(f"{what} needs num_envs to be a multiple of {self._traj_multiple()}")
         if out is None or out["_k"] != k:
             out = self._alloc_trajectory(k)
         out["actions"] = actions
+        tail = (out["_obs"][0].data_ptr(), out["_obs"][1].data_ptr(), out["_rew"][0].data_ptr(), out["_rew"][1].data_ptr(),
+                out["_term"].data_ptr(), self._stats_ptr(), self._episodes.data_ptr(), self._tables_ref, self._stream())
         with torch.cuda.device(dev):
-            _native.check(self._lib.pz_step_many(
-                self._state_ptr, n, self._stride, self._cfg_ref, actions.data_ptr(), k, out["_obs"][0].data_ptr(),
-                out["_obs"][1].data_ptr(), out["_rew"][0].data_ptr(), out["_rew"][1].data_ptr(),
-                out["_term"].data_ptr(), self._stats_ptr(), self._episodes.data_ptr(), self._tables_ref,
-                self._stream()), "pz_step_many")
+            if self.frame_skip > 1:
+                _native.check(self._lib.pz_step_many_held(self._state_ptr, n, self._stride, self._cfg_ref, actions.data_ptr(),
+                                                          k, self.frame_skip, *tail), "pz_step_many_held")
+            else:
+                _native.check(self._lib.pz_step_many(self._state_ptr, n, self._stride, self._cfg_ref, actions.data_ptr(), k,
+                                                     *tail), "pz_step_many")
         if self._scenery is not None:
             self._track_scenery(resync=True)
         self.steps_done += k
