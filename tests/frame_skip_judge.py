@@ -9,12 +9,16 @@ import numpy as np
 
 class HeldOracle:
     """``OracleEnv`` stepped k frames per :meth:`step` on held actions.  Counts, per game and launch, where games ended:
-    ``ended_inside`` (a frame before the last: the rest of the repeat is frozen) and ``ended_last``."""
+    ``ended_inside`` (a frame before the last: the rest of the repeat is frozen) and ``ended_last``.  ``on_frame``
+    (optional; set it on the instance) is called behind every single frame as ``on_frame(j, env, frozen)`` -- the frame's
+    index in the repeat, the oracle env (its ``rew`` / ``term`` / ``state`` are that frame's) and the games the frame
+    found frozen -- and changes nothing here."""
 
     def __init__(self, po, n, k, cfg, nthreads=8):
         self.po, self.k, self.auto_reset = po, int(k), int(cfg.auto_reset)
         self.env = po.OracleEnv(n, cfg, nthreads=nthreads)
         self.ended_inside = self.ended_last = 0
+        self.on_frame = None
 
     def __getattr__(self, name):  # state, reset, episode_returns, episode_lengths, float_rewards ...
         return getattr(self.env, name)
@@ -34,6 +38,8 @@ class HeldOracle:
                     self.ended_last += ended_now
                 else:
                     self.ended_inside += ended_now
+                if self.on_frame is not None:
+                    self.on_frame(j, env, frozen)
                 frozen = term != 0
         finally:
             env.cfg.auto_reset = self.auto_reset

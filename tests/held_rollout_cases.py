@@ -67,6 +67,18 @@ class Case:
         p1, p2 = PLAYERS[self.players]
         return _name(p1, p2, 3 if self.entry == "many" else 2, self.packed, self.obs_format >= 2)
 
+    # what tests/held_configs.py varies and these cases leave alone
+    action_format = "i32"
+
+    @property
+    def stats_ptr(self):
+        """a statistics pointer is passed (here: whenever the stack records statistics)"""
+        return "episode_stats" in STACKS[self.stack]
+
+    def start_state(self):
+        """no planted state: the launch starts from reset plus `preroll` frames of random play"""
+        return None
+
     def oracle_kwargs(self, env_id_base=None):
         p1, p2 = PLAYERS[self.players]
         return dict(winning_score=self.winning_score, is_player1_computer=p1, is_player2_computer=p2,
@@ -131,14 +143,18 @@ BITING = [c for c in CASES if c.bites and c.n <= 4096]
 
 
 def make_judge(oracle, case, lo=0, hi=None, nthreads=8):
-    """The judge of lanes [lo, hi) of `case` at the start of the launch: reset, then `preroll` single frames of random
-    play (their own action stream) with the configured auto_reset -- games are under way, some are over."""
+    """The judge of lanes [lo, hi) of `case` at the start of the launch: reset, then the case's planted state
+    (tests/held_configs.py) or `preroll` single frames of random play (their own action stream) with the configured
+    auto_reset -- games are under way, some are over."""
     from frame_skip_judge import HeldOracle
 
     hi = case.n if hi is None else hi
     base = case.env_id_base + lo
     judge = HeldOracle(oracle, hi - lo, case.hold, oracle.make_config(**case.oracle_kwargs(base)), nthreads=nthreads)
     judge.reset()
+    planted = case.start_state()
+    if planted is not None:
+        judge.env.state[:] = planted[:, lo:hi]
     for f in range(case.preroll):
         judge.env.step(*oracle.random_actions(hi - lo, base, case.action_seed ^ 0xABCD, f, case.n_actions))
     return judge

@@ -14,6 +14,8 @@ levels, and which levels each instantiation can take, and generates a determinis
 
 tests/test_cabi_and_host.py checks those three rules; tests/test_gpu_kernel_configs.py runs every configuration
 through the C ABI against the oracle.  `PZ_CONFIG_SEED` draws another set of configurations (every set meets the rules).
+`plant_states()` is the start of every such launch; tests/held_configs.py reuses the factors, the tables, the ids and that
+recipe for the two frame-skip kernel families.
 """
 from __future__ import annotations
 
@@ -23,6 +25,8 @@ import os
 import random
 import zlib
 from dataclasses import dataclass
+
+import numpy as np
 
 # enum pz_obs_format (include/pikazoo_hip.h)
 OBS_I32, OBS_F32_NORM, OBS_I16, OBS_F16, OBS_BF16, OBS_F16_NORM, OBS_BF16_NORM = range(7)
@@ -166,6 +170,69 @@ class Config:
         if self.entry == "pz_step":
             lv["action_format"] = self.action_format
         return lv
+
+
+def random_valid_states(n, rng):
+    """int32[44, n]: every attribute at random over its valid range (players' (y, y_velocity) from the pairs a jump or
+    a dive passes through), half of the balls next to a player -- the whole state space, reachable or not."""
+    st = np.zeros((44, n), np.int32)
+    for base, lo, hi in ((0, 32, 184), (13, 248, 400)):
+        st[base + 0] = rng.integers(lo, hi + 1, n)
+        st[base + 3] = rng.integers(0, 5, n)
+        steps = rng.integers(0, 33, n)
+        v0 = np.where(rng.random(n) < 0.7, -16, -5)
+        y, v = np.full(n, 244), v0.copy()
+        for k in range(33):
+            move = (k < steps) & (y + v <= 244)
+            y, v = np.where(move, y + v, y), np.where(move, v + 1, v)
+        ground = np.isin(st[base + 3], (0, 4)) & (rng.random(n) < 0.7)
+        st[base + 1], st[base + 2] = np.where(ground, 244, y), np.where(ground, 0, v)
+        st[base + 4] = rng.integers(0, 5, n)
+        st[base + 5] = rng.choice([-1, 1], n)
+        st[base + 6] = rng.integers(0, 6, n)
+        st[base + 7] = rng.integers(-1, 2, n)
+        st[base + 8] = rng.integers(-1, 4, n)
+        st[base + 9] = rng.integers(0, 2, n)
+        st[base + 10] = rng.integers(0, 5, n)
+        st[base + 11] = rng.integers(0, 2, n)
+        st[base + 12] = rng.integers(0, 2, n)
+    near = rng.random(n) < 0.5
+    who = rng.random(n) < 0.5
+    px, py = np.where(who, st[0], st[13]), np.where(who, st[1], st[14])
+    st[26] = np.where(near, np.clip(px + rng.integers(-40, 41, n), 20, 432), rng.integers(20, 433, n))
+    st[27] = np.where(near, np.clip(py + rng.integers(-40, 41, n), 0, 252), rng.integers(0, 253, n))
+    st[28] = rng.integers(-20, 21, n)
+    st[29] = np.where(rng.random(n) < 0.8, rng.integers(-120, 121, n), rng.integers(-300, 301, n))
+    st[30] = rng.integers(0, 2, n)
+    st[31], st[32] = rng.integers(20, 433, n), rng.integers(-100, 253, n)
+    st[33], st[34] = rng.integers(20, 433, n), rng.integers(-100, 253, n)
+    st[35] = rng.integers(0, 51, n)
+    st[36] = rng.integers(20, 433, n)
+    st[37] = rng.integers(20, 433, n)
+    st[38], st[39] = rng.integers(0, 3, n), rng.integers(0, 3, n)
+    st[40] = rng.integers(0, 2, n)
+    st[43] = rng.integers(4, 1 << 20, n)
+    return st
+
+
+def plant_states(c, n=None):
+    """(planted int32[44, n], over bool[n]): the start of configuration `c`'s launch, drawn from `c.seed` --
+    random_valid_states, then (but on the matrix rows) scores below the winning score with a quarter of the games one
+    point from the end, and an eighth of the games over: a winner at the winning score, game_ended and round_ended set.
+    Those are reset in place before their first frame, or stay frozen without auto_reset."""
+    n = c.n if n is None else n
+    rng = np.random.default_rng(c.seed)
+    ws = c.winning_score
+    planted = random_valid_states(n, rng)
+    over = rng.random(n) < 0.125
+    winner = np.where(rng.random(n) < 0.5, 38, 39)
+    if not c.matrix:
+        planted[38:40] = rng.integers(0, ws, (2, n))
+        near = np.flatnonzero(rng.random(n) < 0.25)
+        planted[38 + rng.integers(0, 2, near.size), near] = ws - 1
+    planted[winner[over], np.flatnonzero(over)] = ws
+    planted[41][over] = planted[42][over] = 1
+    return planted, over
 
 
 def _with(row, levels: dict, name: str, seed: int, tables=None) -> Config:

@@ -1,5 +1,7 @@
 """GPU tests (``-m gpu``) of frame skip: ``pikazoo_v0.env(frame_skip=k)`` holds each action for k frames in one launch
-(``pz_step_held``, the ``hold_kernel`` family).
+(``pz_step_held``, the ``hold_kernel`` family) through the Python env, over the structure of a launch -- k, player mix, table
+mode, state and row format, the fused stacks -- from reset plus random play (the runtime configurations of every
+instantiation, from planted states and straight through the C ABI: tests/test_gpu_held_configs.py).
 
 The judge is the CPU oracle driven as the loop that defines the feature (tests/frame_skip_judge.py: per step k oracle
 frames on the same actions, the first with the configured ``auto_reset``, the rest with 0, rewards summed in numpy

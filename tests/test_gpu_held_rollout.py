@@ -1,5 +1,7 @@
 """GPU tests (``-m gpu``) of the k-step trajectory launches of a frame-skip env: ``pz_step_many_held`` /
-``pz_rollout_random_held`` (the ``held_traj_kernel`` family) and ``raw_env.step_many_held`` / ``rollout_random_held``.
+``pz_rollout_random_held`` (the ``held_traj_kernel`` family) and ``raw_env.step_many_held`` / ``rollout_random_held``, on
+the structural cases of tests/held_rollout_cases.py (the runtime configurations of every instantiation, from planted
+states: tests/test_gpu_held_configs.py, through ``Launch`` / ``check_case`` here).
 
 The judge is ``HeldOracle`` (tests/frame_skip_judge.py): the CPU oracle driven as the loop that defines frame skip,
 pinned to the unmodified reference by tests/golden/frame_skip_k4.npz.  Every launch is compared with it slab by slab and
@@ -16,7 +18,9 @@ import torch
 from torch.profiler import ProfilerActivity, profile
 
 from frame_skip_judge import HeldOracle
+from held_configs import hold_kernels
 from held_rollout_cases import CASES, N_ABOVE, STACKS, TABLE, held_traj_kernels, judge_counts, make_judge, policy
+from kernel_configs import ACTION_FORMATS
 
 pytestmark = pytest.mark.gpu
 
@@ -51,8 +55,13 @@ def tables_of(mode, dev):
             "none": lambda: None}[mode]()
 
 
+ACTION_DTYPES = {"i32": torch.int32, "i64": torch.int64, "u8": torch.uint8, "i16": torch.int16}
+
+
 class Launch:
-    """One launch of `c` through the C ABI from `start` ([44][n] int32, the judge's state) into sentinel-filled buffers."""
+    """One launch of `c` (a held_rollout_cases.Case or a held_configs.HeldConfig) through the C ABI from `start`
+    ([44][n] int32, the judge's state) into sentinel-filled buffers.  ``pz_step_held`` (entry "held"): k launches in a
+    row, launch t on row t of the tape in the caller's element type, into output slot t."""
 
     def __init__(self, c, oracle, start, stats0, tape=None):
         from pikazoo_amd import _native
@@ -63,7 +72,7 @@ class Launch:
         self.n, self.stride = n, n + c.stride_pad
         stride = self.stride
         self.cfg = _native.PzConfig.from_buffer_copy(oracle.make_config(**c.oracle_kwargs()))
-        self.cfg.packed_state, self.cfg.normalize_obs, self.cfg.action_format = int(c.packed), fmt, 0
+        self.cfg.packed_state, self.cfg.normalize_obs, self.cfg.action_format = int(c.packed), fmt, ACTION_FORMATS[c.action_format]
         self.faults = torch.zeros(1, dtype=torch.int64, device=dev)
         self.cfg.action_faults = self.faults.data_ptr()
         self.tables = tables_of(c.tables, dev)
@@ -78,7 +87,7 @@ class Launch:
                                           misfits.data_ptr(), self.stream) == 0
             torch.cuda.synchronize()
             assert int(misfits.item()) == 0
-        self.with_stats = "episode_stats" in STACKS[c.stack]
+        self.with_stats = c.stats_ptr  # (a statistics mode without a pointer: nothing may be written through it)
         self.stats = torch.zeros(20 * stride, dtype=torch.uint8, device=dev)
         self.ret = self.stats[:16 * stride].view(torch.float64).view(2, stride)
         self.lengths = self.stats[16 * stride:].view(torch.int32)
@@ -92,6 +101,10 @@ class Launch:
         self.act = torch.full((k * 2 * n + PAD,), SENT, dtype=torch.int32, device=dev)
         self.done = torch.zeros(1, dtype=torch.int64, device=dev)
         self.tape = None if tape is None else torch.from_numpy(np.ascontiguousarray(tape, np.int32)).to(dev)
+        if c.entry == "held":
+            self.tape = self.tape.to(ACTION_DTYPES[c.action_format]).contiguous()
+        else:
+            assert c.action_format == "i32"  # the tape of a trajectory launch is int32 alone
         torch.cuda.synchronize()
 
     def run(self):
@@ -99,10 +112,21 @@ class Launch:
         sp = self.stats.data_ptr() if self.with_stats else None
         tb = None if self.tables is None else C.byref(self.tables)
         state_ptr = self.packed.data_ptr() if c.packed else self.state.data_ptr()
-        outs = (self.obs[0].data_ptr(), self.obs[1].data_ptr(), self.rew[0].data_ptr(), self.rew[1].data_ptr(),
-                self.term.data_ptr(), sp, self.done.data_ptr(), tb, self.stream)
+        n = self.n
+
+        def slot(t):  # the outputs of pz_step_held's launch t
+            return (self.obs[0][t * n * OBS:].data_ptr(), self.obs[1][t * n * OBS:].data_ptr(), self.rew[0][t * n:].data_ptr(),
+                    self.rew[1][t * n:].data_ptr(), self.term[t * n:].data_ptr(), sp, self.done.data_ptr(), tb, self.stream)
+
+        outs = slot(0)
+        launches = c.k if c.entry == "held" else 1
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            if c.entry == "many":
+            if c.entry == "held":
+                for t in range(c.k):
+                    err = lib.pz_step_held(state_ptr, n, self.stride, C.byref(self.cfg), self.tape[t, 0].data_ptr(),
+                                           self.tape[t, 1].data_ptr(), c.hold, *slot(t))
+                    assert err == 0, (c.id, t, err)
+            elif c.entry == "many":
                 err = lib.pz_step_many_held(state_ptr, self.n, self.stride, C.byref(self.cfg), self.tape.data_ptr(), c.k,
                                             c.hold, *outs)
             else:
@@ -112,9 +136,9 @@ class Launch:
             torch.cuda.synchronize()
         device_events = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
         assert device_events, "torch.profiler recorded no device kernel: the dispatched-kernel check cannot run"
-        assert [kernel_name(e.name) for e in device_events if "pz::" in e.name] == [c.kernel], \
+        assert [kernel_name(e.name) for e in device_events if "pz::" in e.name] == [c.kernel] * launches, \
             (c.id, sorted({e.name for e in device_events}))
-        assert c.kernel in held_traj_kernels()
+        assert c.kernel in (hold_kernels() if c.entry == "held" else held_traj_kernels())
 
     def check_nothing_written_outside(self):
         c, n, stride, k = self.c, self.n, self.stride, self.c.k
@@ -146,7 +170,14 @@ class Launch:
 def check_case(c, oracle):
     """Launch `c`, then judge it: every slab's rows, rewards and `terminated`, the actions pz_rollout_random_held writes,
     the final state, the statistics, episodes_done (all exact, on every lane), nothing outside lane n / slab k, and --
-    hold > 1, k >= 16 -- the judge's own counters say that the case bit."""
+    hold > 1, k >= 16 -- the judge's own counters say that the case bit.  Returns the judge's counts (judge_counts).
+
+    On top of the bit-for-bit comparison, float32 rewards under auto_reset are held against the float64 sum of the
+    judge's per-frame float32 rewards r_1 .. r_hold, within ``hold * 2**-24 * sum(|r_j|)``.  Derivation: the device sums
+    in frame order from +0.0f, s_j = fl(s_{j-1} + r_j).  The first add is exact.  Every later one is off by at most half
+    an ulp of its result, 2**-24 times a partial sum that is itself bounded by T = sum(|r_j|) plus the error so far:
+    e_j <= e_{j-1} (1 + 2**-24) + 2**-24 T, so e_hold <= T ((1 + 2**-24)**(hold - 1) - 1) < hold * 2**-24 * T for every
+    hold below 2**12.  A frame counted twice, dropped, or summed into the wrong slab misses it by a whole reward."""
     n, k, fmt = c.n, c.k, c.obs_format
     # the judge runs the whole batch (the exact episodes_done, every lane's rewards / flags / actions / final state); the
     # observation rows are compared on every lane below the size switch, on three slices of 512 lanes at and above it
@@ -155,7 +186,7 @@ def check_case(c, oracle):
     start = judge.state.copy()
     stats0 = None if judge.env.stats is None else judge.env.stats.copy()
     tape = None
-    if c.entry == "many":
+    if c.entry in ("many", "held"):
         tape = np.stack([np.stack(policy(oracle, c, t)) for t in range(k)])  # [k][2][n]
     run = Launch(c, oracle, start, stats0, tape)
     run.run()
@@ -168,6 +199,18 @@ def check_case(c, oracle):
     h_act = cpu(run.act[:k * 2 * n].view(k, 2, n)) if c.entry == "rollout" else None
     terms, ended = [], 0
     frozen = (judge.state[oracle.E_GAME_ENDED] != 0) & (not c.auto_reset)
+    judge64 = judge.float_rewards and bool(c.auto_reset)
+    sum64, abs64 = np.zeros((2, n)), np.zeros((2, n))
+
+    def on_frame(j, env, _):  # the float64 judge of a slab's reward: the frame rewards, exactly
+        if j == 0:
+            sum64[:], abs64[:] = 0.0, 0.0
+        for p in range(2):
+            sum64[p] += env.rew[p].astype(np.float64)
+            abs64[p] += np.abs(env.rew[p].astype(np.float64))
+
+    if judge64:
+        judge.on_frame = on_frame
     for t in range(k):
         a1, a2 = policy(oracle, c, t)
         if h_act is not None:
@@ -179,6 +222,11 @@ def check_case(c, oracle):
                     (c.id, lo, t, f"observations of player {p + 1}")
             assert rrew[p].dtype == (np.float32 if judge.float_rewards else np.int32)
             assert np.array_equal(h_rew[p][t], rrew[p].view(np.int32)), (c.id, t, f"rewards of player {p + 1}")
+            if judge64:
+                err = np.abs(h_rew[p][t].view(np.float32).astype(np.float64) - sum64[p])
+                bound = c.hold * 2.0 ** -24 * abs64[p]
+                assert bool((err <= bound).all()), \
+                    (c.id, t, f"rewards of player {p + 1} vs float64: {err.max()} (bound {bound[err.argmax()]})")
         assert np.array_equal(h_term[t], rterm), (c.id, t, "terminations")
         ended += int(((rterm != 0) & ~frozen).sum())
         frozen = (rterm != 0) & (not c.auto_reset)
@@ -200,6 +248,7 @@ def check_case(c, oracle):
             assert revived > 0, "no game was terminated in one slab and running in the next"
     if c.ends_twice:
         assert twice > 0, "no game ended twice inside the launch"
+    return inside, last, revived, twice
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c.id)

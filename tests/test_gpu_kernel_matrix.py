@@ -20,9 +20,8 @@ import pytest
 import torch
 from torch.profiler import ProfilerActivity, profile
 
-from kernel_configs import ACTION_FORMATS, NORMAL_STATE_REWARD, NORMALIZED, SHAPING
+from kernel_configs import ACTION_FORMATS, NORMAL_STATE_REWARD, NORMALIZED, SHAPING, plant_states
 from kernel_matrix import ROWS, STRIDE_PAD
-from test_gpu_packed import _random_valid_states
 from test_gpu_parity import cpu
 
 pytestmark = pytest.mark.gpu
@@ -130,21 +129,12 @@ def check_config(c, oracle, buffers):
     launches, frames = _slots(c)
     slots = launches * frames
     b = buffers(n)
-    rng = np.random.default_rng(c.seed)
     base, aseed, t0, ws = c.env_id_base, c.seed ^ 0x5EED, c.t0, c.winning_score
     n_act = 13 if c.simplify_action else 18
 
-    planted = _random_valid_states(n, rng)
-    # an eighth of the games over (a winner at the winning score; game_ended implies round_ended): reset in place
-    # before their first frame, or frozen without auto_reset
-    over = rng.random(n) < 0.125
-    winner = np.where(rng.random(n) < 0.5, 38, 39)
-    if not c.matrix:
-        planted[38:40] = rng.integers(0, ws, (2, n))
-        near = np.flatnonzero(rng.random(n) < 0.25)
-        planted[38 + rng.integers(0, 2, near.size), near] = ws - 1
-    planted[winner[over], np.flatnonzero(over)] = ws
-    planted[41][over] = planted[42][over] = 1
+    # random valid states, scores below the winning score, an eighth of the games over: reset in place before their first
+    # frame, or frozen without auto_reset (kernel_configs.plant_states, shared with the frame-skip configurations)
+    planted, over = plant_states(c)
     frozen = over & (c.auto_reset == 0)
     okw = c.oracle_kwargs()
     cfg = _native.PzConfig.from_buffer_copy(oracle.make_config(env_id_base=base, **okw))
