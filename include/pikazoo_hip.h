@@ -267,6 +267,26 @@ int pz_step(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
             uint8_t *terminated, void *episode_stats, const pz_flight_tables *tables,
             void *stream);
 
+/* ---- pz_step with the computer players chosen per game ------------------------------------
+ * Exactly pz_step, with cfg->p1_computer / cfg->p2_computer ignored and read per game from computer_mask[i] & 3:
+ * bit 0 = player 1 of game i is the rule-based computer, bit 1 = player 2 (uint8[n], device; NULL: PZ_E_NULL).  Game
+ * i's frame is the frame of the reference env constructed with its two flags -- games share nothing and a game's draws
+ * depend on its global id alone -- so a batch may mix self-play, either computer opponent and computer vs computer,
+ * and the mask may be rewritten between launches: a game continues from its state with the new roles.
+ *   - both actions are read and range-checked for every game (pikazoo_env.py:182-184; cfg->action_faults counts an
+ *     out-of-range action on a computer side too); a computer side's decision replaces its decoded input;
+ *   - expected_landing_point_x (state word 36) is rewritten only in games with a computer player
+ *     (physics.py:314-315, :331-332): a game without one keeps its value;
+ *   - a decision's draws advance the game's rng_draw_counter only for its computer sides, player 1's first.
+ * Every other rule of pz_step holds: formats, alignment, `tables` NULL or either table NULL, episode_stats.
+ * One wave per 64 games at every batch size; waves whose games have no computer player run the human-vs-human
+ * frame.  Single frames only: the k-frame and held launches take cfg's two flags. */
+int pz_step_mixed(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg,
+                  const uint8_t *computer_mask, const void *act_p1, const void *act_p2,
+                  int32_t *obs_p1, int32_t *obs_p2, void *rew_p1, void *rew_p2,
+                  uint8_t *terminated, void *episode_stats, const pz_flight_tables *tables,
+                  void *stream);
+
 /* ---- pz_step with its arguments prepared once ---------------------------------------------
  * A per-step caller (raw_env.step, pikazoo_env.py:175-240, is called once per frame) hands over the same twelve
  * buffers and the same configuration every time; only the two action vectors and the stream change.  pz_step_bind

@@ -2616,6 +2616,113 @@ static pz_flight_tables tables_of(const pz_flight_tables* t)
 
 }  // namespace pz
 
+// ---- per-game computer players: one frame of a batch whose games differ in who plays (pz_step_mixed) ----------------
+// Lane by lane pz_step with cfg.p1_computer / p2_computer read from the game's role code (uint8: bit 0 = player 1 is
+// the computer, bit 1 = player 2) instead of the configuration: games share nothing and a game's draws depend on its
+// global id alone.  One wave per 64 games at every batch size, both decisions compiled in (mixed_frame_head /
+// mixed_frame_tail, pz_physics.hpp); the code is loaded with the lane's actions, under the state loads.  Two
+// instantiations, by state format; observation format and action element type are wave-uniform run-time branches as in
+// every single-frame kernel.  No scout wave: without the power-hit table the candidates are computed in this wave
+// (hold_kernel does the same).  A namespace of its own: the pz:: kernels of the code object are the swept 177
+// (tests/test_held_configs_host.py); this family's sweep and census are tests/test_mixed_host.py / test_gpu_mixed.py.
+namespace pz_mixed {
+using namespace pz;
+
+template <bool PACKED>
+__global__ __launch_bounds__(kLanes) __attribute__((amdgpu_waves_per_eu(1, 8)))
+void step_mixed_kernel(PZ_HOT_PARAMS, const uint8_t* computer_mask, const StepArgs a)
+{
+    const HotArgs hot{state, n, stride, act_p1, act_p2, act_format};
+    __shared__ __attribute__((aligned(16))) int32_t lds_obs[2][kLanes * PZ_OBS_DIM];
+
+    const int lane = threadIdx.x & (kLanes - 1);
+    const int64_t i = (int64_t)blockIdx.x * kLanes + lane;
+    const bool live = i < hot.n;
+    const uint32_t n32 = (uint32_t)hot.n;
+
+    // descriptors are built from kernel arguments only, so they are provably wave-uniform
+    const StateIO io{make_rsrc(hot.state, PACKED ? 0u : (uint32_t)(hot.stride * (PZ_STATE_WORDS * 4))),
+                     (uint32_t)hot.stride * 4u, (uint32_t)i * 4u};
+    const PackedIO pio = make_packed_io(hot.state, PACKED ? hot.stride : 0, i);
+    const bool as_float = a.cfg.ballpos_reward != 0 || a.cfg.normal_state_mode != 0;
+    const bool with_stats = a.episode_stats != nullptr && a.cfg.episode_stats_mode != 0;  // uniform
+    const StatsIO sio = make_stats_io(a.episode_stats, with_stats, a.stride, i);
+
+    Game g{};
+    const RngId id = make_rng_id(a.cfg, live ? i : 0);
+    const FlightLut lut = make_lut(a.tables);
+    int a1 = 0, a2 = 0;
+    uint32_t act_high = 0u;
+    load_actions(hot.act_p1, hot.act_p2, n32, (uint32_t)i, hot.act_format, a1, a2, act_high);
+    // (rows past n read as 0: no computer player)
+    const uint32_t code = __builtin_amdgcn_raw_buffer_load_b8(make_rsrc(computer_mask, n32), (uint32_t)i, 0, 0);
+    EpisodeStats st{0.0, 0.0, 0};
+    PackedWords was{};
+    if (live) {
+        if constexpr (PACKED)
+            was = load_game_packed(g, pio, true);
+        else
+            load_game(g, io);
+        if (with_stats) sio.load(st);
+    }
+    const Game loaded = g;  // what the columns held before the frame
+    LaneRoles roles;
+    roles.c1 = (code & 1u) != 0u;
+    roles.c2 = (code & 2u) != 0u;
+    roles.any1 = __builtin_amdgcn_ballot_w64(roles.c1) != 0ull;
+    roles.any2 = __builtin_amdgcn_ballot_w64(roles.c2) != 0ull;
+
+    // lds_obs[0] doubles as the wave's cooperative scratch (power-hit candidates without the table) until the
+    // observations are staged
+    const bool resets = live && g.e.game_ended != 0 && a.cfg.auto_reset != 0;
+    FrameHead head = mixed_frame_head(g, a.cfg, id, live, lane, lut, roles);
+    const bool frozen = head.frozen;
+    const int reward = mixed_frame_tail(g, a.cfg, id, a1, a2, live, head, lds_obs[0], lane, lut, roles);
+    const unsigned int finished = (unsigned int)(live && g.e.game_ended && !frozen);
+    const Rewards rw = shape_rewards(a.cfg, g, reward, frozen);
+    if (with_stats) stats_update(st, a.cfg, rw, resets, live && !frozen, as_float);
+
+    if (live) {
+        if constexpr (PACKED)
+            store_game_packed(g, pio, was, true);
+        else
+            store_game_changed(g, loaded, io);
+        if (with_stats) sio.store(st);
+    }
+    emit_outputs(a, g, rw, as_float, live, i, lane, 0, lds_obs);
+
+    // both given actions are range-checked on every lane, computer or not
+    count_action_faults(a.cfg, live && actions_out_of_range(a.cfg, a1, a2, act_high));
+    if (a.episodes_done != nullptr) {
+        // one atomic per wave: reduce the per-lane counts across the wavefront first
+        unsigned int total = finished;
+        for (int off = kLanes / 2; off > 0; off >>= 1) total += __shfl_down(total, off, kLanes);
+        if (lane == 0 && total != 0) atomicAdd(a.episodes_done, (unsigned long long)total);
+    }
+}
+
+// A diagnostic subset build (dev_keep) leaves the family out, as the held families: neither kernel is instantiated.
+using MixedKernelFn = void (*)(PZ_HOT_PARAMS, const uint8_t*, const StepArgs);
+template <bool PACKED>
+constexpr MixedKernelFn mixed_kernel()
+{
+    if constexpr (diag::kSubset != 0u)
+        return nullptr;
+    else
+        return step_mixed_kernel<PACKED>;
+}
+constexpr MixedKernelFn kMixedKernels[2] = {mixed_kernel<false>(), mixed_kernel<true>()};
+
+static int launch_mixed(const StepArgs& a, const uint8_t* computer_mask, hipStream_t stream)
+{
+    const MixedKernelFn kernel = kMixedKernels[is_packed(a.cfg) ? 1 : 0];
+    if (kernel == nullptr) return PZ_E_CONFIG;  // left out of a diagnostic build
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(a.n, kLanes)), dim3(kLanes), 0, stream, PZ_HOT_ARGS(a), computer_mask, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace pz_mixed
+
 using namespace pz;
 
 extern "C" {
@@ -2773,6 +2880,20 @@ int pz_step(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, con
     StepArgs a{state,  n,          stride,        act_p1,  act_p2, 0, 0, 1, nullptr, obs_p1, obs_p2, rew_p1,
                rew_p2, terminated, episode_stats, nullptr, tables_of(tables), *cfg};
     return launch_step(kActions, a, (hipStream_t)stream);
+}
+
+int pz_step_mixed(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, const uint8_t* computer_mask,
+                  const void* act_p1, const void* act_p2, int32_t* obs_p1, int32_t* obs_p2, void* rew_p1, void* rew_p2,
+                  uint8_t* terminated, void* episode_stats, const pz_flight_tables* tables, void* stream)
+{
+    if (int e = check_common(state, n, stride, cfg)) return e;
+    if (!computer_mask || !act_p1 || !act_p2 || !obs_p1 || !obs_p2 || !rew_p1 || !rew_p2 || !terminated) return PZ_E_NULL;
+    if (misaligned16(obs_p1) || misaligned16(obs_p2)) return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    if (tables_misaligned(tables)) return PZ_E_ALIGN;
+    StepArgs a{state,  n,          stride,        act_p1,  act_p2, 0, 0, 1, nullptr, obs_p1, obs_p2, rew_p1,
+               rew_p2, terminated, episode_stats, nullptr, tables_of(tables), *cfg};
+    return pz_mixed::launch_mixed(a, computer_mask, (hipStream_t)stream);
 }
 
 // pz_step with its arguments prepared once: the block holds the StepArgs pz_step would build

@@ -1122,6 +1122,8 @@ __device__ __forceinline__ FrameHead frame_head(Game& g, const pz_config& cfg, c
     return h;
 }
 
+// TWIN: mixed_frame_tail (below) repeats this function's non-table decisions and everything from player 2's move on --
+// both collisions, scoring, round / game end -- with the roles per lane.  A change to the frame here is made there too.
 // PIN: the caller runs head and tail back to back (single frame): keep the head's Philox blocks under its gathers
 template <bool AI1, bool AI2, int SCOUT = kNoScout, bool PIN = true>
 __device__ __forceinline__ int frame_tail(Game& g, const pz_config& cfg, const RngId& id, int a1, int a2, bool live,
@@ -1276,6 +1278,145 @@ __device__ __forceinline__ int step_games(Game& g, const pz_config& cfg, const R
     FrameHead h = frame_head<AI1, AI2, SCOUT>(g, cfg, id, live, lane, lut, link, nullptr);
     frozen = h.frozen;
     return frame_tail<AI1, AI2, SCOUT, true>(g, cfg, id, a1, a2, live, h, scratch, lane, lut, link, ex_pending, last_frame);
+}
+
+// ---------------------------------------------------------------------------------------
+// The same frame with the computer players chosen PER LANE (pz_step_mixed): lane by lane the frame of
+// frame_head / frame_tail<c1, c2>, both decisions compiled in and selected by the lane's two role bits.
+//   * the landing point is predicted in front of the decisions (:314-315) and after a collision (:331-332) only by a
+//     lane with a computer player: a lane without one keeps its state word;
+//   * a decision's draws advance the lane's counter only for its computer sides, player 1's first; player 2's
+//     pre-drawn block starts at the counter player 1 left, whether player 1 drew or not;
+//   * player 2's decision reads player 1's x after its move, whoever moved it;
+//   * both actions are decoded for every lane (pikazoo_env.py:182-184); a computer side's decision replaces its input.
+// any1 / any2 (wave-uniform): some lane of the wave has a computer player 1 / 2.  A wave without one runs exactly the
+// human-vs-human frame -- no gather, no decision --, a wave with none on one side skips that side's decision.
+// Single frame, no scout wave: with the power-hit table the head's gathers and the pre-drawn decisions of frame_tail's
+// table path, without it the wave-cooperative candidates.  Kept apart from frame_tail, whose instruction streams in
+// the shipped kernels stay as they are; the building blocks are shared.
+// TWIN: frame_tail<AI1, AI2>.  The non-table decision path and everything from player 2's move on (both collisions,
+// scoring, round / game end) are that function's lines: a change to the frame is made in both.
+// ---------------------------------------------------------------------------------------
+struct LaneRoles {
+    bool c1, c2;      // this lane's player 1 / 2 is the computer
+    bool any1, any2;  // wave-uniform: some lane's is
+};
+
+__device__ __forceinline__ FrameHead mixed_frame_head(Game& g, const pz_config& cfg, const RngId& id, bool live, int lane,
+                                                      const FlightLut& lut, const LaneRoles roles)
+{
+    // round start (every lane draws both boldnesses and the serve, as now) and the ball-world step: the head without a
+    // computer player issues no gather
+    FrameHead h = frame_head<false, false>(g, cfg, id, live, lane, lut, ScoutLink{nullptr, nullptr, nullptr}, nullptr);
+    const bool active = live && !h.frozen;
+    if ((roles.any1 || roles.any2) && lut.has_power_hit && active) {  // (wave-uniform but for `active`)
+        const bool scan = (roles.c1 && power_hit_scan_needed(g.p1, g.b)) || (roles.c2 && power_hit_scan_needed(g.p2, g.b));
+        h.landing_word = lut.landing_issue(roles.c1 | roles.c2, g.b.x, g.b.y, g.b.xv, g.b.yv).value;
+        h.candidate_row = lut.candidates_issue(scan, g.b.x, g.b.y, abs(g.b.yv)).value;
+        h.pre = predraw3(id, g.e.rng);
+    }
+    return h;
+}
+
+__device__ __forceinline__ int mixed_frame_tail(Game& g, const pz_config& cfg, const RngId& id, int a1, int a2, bool live,
+                                                FrameHead& h, int32_t* __restrict__ scratch, int lane, const FlightLut& lut,
+                                                const LaneRoles roles)
+{
+    const bool active = live && !h.frozen, ground = h.ground;
+    const bool c1 = roles.c1, c2 = roles.c2, any = roles.any1 || roles.any2;
+    Input in1{0, 0, 0}, in2{0, 0, 0};
+    if (active) {
+        // :182-184 -- every player's key state is sampled, computer-controlled or not
+        if (cfg.simplify_action) {
+            in1 = decode_action(kSimpleTablesP1, a1, g.p1.hitprev);
+            in2 = decode_action(kSimpleTablesP2, a2, g.p2.hitprev);
+        } else {
+            in1 = decode_action(kFullTables, a1, g.p1.hitprev);
+            in2 = decode_action(kFullTables, a2, g.p2.hitprev);
+        }
+    }
+    if (any && lut.has_power_hit) {  // wave-uniform
+        if (active) {
+            int ex[6] = {0, 0, 0, 0, 0, 0};
+            asm volatile("" : "+v"(h.pre.w0), "+v"(h.pre.w1), "+v"(h.pre.w2), "+v"(h.landing_word), "+v"(h.candidate_row.x),
+                         "+v"(h.candidate_row.y), "+v"(h.candidate_row.z));  // (see step_games_pair)
+            // what the head's gathers were issued for, re-derived (nobody has moved since)
+            const bool scan1 = c1 && power_hit_scan_needed(g.p1, g.b);
+            const bool scan2 = c2 && power_hit_scan_needed(g.p2, g.b);
+            const int ayv = abs(g.b.yv);
+            uint32_t unused;
+            LandingProbe lp = lut.landing_locate(c1 | c2, g.b.x, g.b.y, g.b.xv, g.b.yv, unused);
+            lp.value = h.landing_word;
+            CandidateProbe cp = lut.candidates_locate(scan1 | scan2, g.b.x, g.b.y, ayv, unused);
+            cp.value = h.candidate_row;
+            g.b.ex = lut.landing_finish(lp, g.b.x, g.b.y, g.b.xv, g.b.yv, g.b.ex);  // a lane without a computer keeps its word
+            lut.candidates_finish(cp, g.b.x, g.b.y, ayv, ex);
+            PreDrawn pre = h.pre;
+            if (roles.any1) {
+                const int standby = g.p1.standby;
+                Input decided;
+                const uint32_t draws = computer_decide_predrawn<false>(g.p1, g.b, g.p2.x, pre, scan1, ex, decided);
+                g.p1.standby = c1 ? g.p1.standby : standby;
+                in1 = Input{c1 ? decided.xd : in1.xd, c1 ? decided.yd : in1.yd, c1 ? decided.hit : in1.hit};  // (by field: registers)
+                g.e.rng += c1 ? draws : 0u;
+            }
+            player_move<false>(g.p1, in1);
+            if (roles.any2) {
+                if (roles.any1) pre = predraw3(id, g.e.rng);  // player 2's draws start where player 1 left the counter
+                const int standby = g.p2.standby;
+                Input decided;
+                const uint32_t draws = computer_decide_predrawn<true>(g.p2, g.b, g.p1.x, pre, scan2, ex, decided);
+                g.p2.standby = c2 ? g.p2.standby : standby;
+                in2 = Input{c2 ? decided.xd : in2.xd, c2 ? decided.yd : in2.yd, c2 ? decided.hit : in2.hit};
+                g.e.rng += c2 ? draws : 0u;
+            }
+        }
+    } else {
+        // :314-315: the ball does not move between the two players' calls, one evaluation serves both
+        if (active && (c1 | c2)) g.b.ex = lut.landing_x(g.b.x, g.b.y, g.b.xv, g.b.yv);
+        if (roles.any1) {
+            HitScan hs{false, false};
+            int ex[6] = {0, 0, 0, 0, 0, 0};
+            if (active && c1) hs = computer_decide_begin<false>(g.p1, g.b, in1, id, g.e.rng);
+            wave_power_hit_candidates(hs.need, g.b, ex, scratch, lane);
+            computer_decide_finish<false>(hs, ex, g.p1, g.p2, in1);
+        }
+        if (active) player_move<false>(g.p1, in1);
+        if (roles.any2) {
+            HitScan hs{false, false};
+            int ex[6] = {0, 0, 0, 0, 0, 0};
+            if (active && c2) hs = computer_decide_begin<true>(g.p2, g.b, in2, id, g.e.rng);
+            wave_power_hit_candidates(hs.need, g.b, ex, scratch, lane);
+            computer_decide_finish<true>(hs, ex, g.p2, g.p1, in2);
+        }
+    }
+
+    int reward = 0;
+    if (active) {
+        player_move<true>(g.p2, in2);
+
+        // physics.py:319-335: player 1 first, then player 2 against the possibly changed velocities
+        const bool touch1 = ball_touches_player(g.b, g.p1), hit1 = touch1 & (g.p1.coll == 0);
+        ball_player_collision(g.b, hit1, g.p1.x, in1, g.p1.state, id, g.e.rng);
+        g.p1.coll = touch1;
+        const bool touch2 = ball_touches_player(g.b, g.p2), hit2 = touch2 & (g.p2.coll == 0);
+        ball_player_collision(g.b, hit2, g.p2.x, in2, g.p2.state, id, g.e.rng);
+        g.p2.coll = touch2;
+
+        // scoring / round end / game end (:190-210); round_ended and game_ended are both 0 here
+        const bool p2_scores = ground & (g.b.punch < kGroundHalfWidth), p1_scores = ground & !p2_scores;
+        g.e.s1 += p1_scores;
+        g.e.s2 += p2_scores;
+        g.e.p2serve = ground ? (int)p2_scores : g.e.p2serve;
+        g.e.game_ended = ground & ((p2_scores ? g.e.s2 : g.e.s1) >= cfg.winning_score);
+        g.e.round_ended = ground;
+        reward = ground ? (p2_scores ? -1 : 1) : 0;
+
+        // :331-332 -- after a processed collision, in a game with a computer player (one evaluation behind both
+        // collisions leaves what the second of two would)
+        if ((c1 | c2) && (hit1 | hit2)) g.b.ex = lut.landing_x(g.b.x, g.b.y, g.b.xv, g.b.yv);
+    }
+    return reward;
 }
 
 // ---------------------------------------------------------------------------------------

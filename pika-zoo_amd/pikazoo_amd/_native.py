@@ -78,6 +78,8 @@ _SIGNATURES = {
     "pz_unpack_state": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P]),
     # (the argument before the stream is `const pz_flight_tables*`: a byref(PzFlightTables) or None)
     "pz_step": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # (per-game computer players: pz_step's arguments + the uint8[n] role codes in front of the actions)
+    "pz_step_mixed": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pz_step_bound_bytes": (C.c_int64, []),
     "pz_step_bind": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, _P, _P, _P, _P, _P, _P]),
     "pz_step_bound": (C.c_int, [_P, _P, _P, _P]),

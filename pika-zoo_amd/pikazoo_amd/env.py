@@ -60,6 +60,19 @@ _E_SCORE_P1 = 38
 _E_GAME_ENDED = 42
 
 
+def _per_game_roles(value, n: int, name: str):
+    """``is_player?_computer=``: a scalar as its truth value (one choice for the batch), or the per-game choice as a uint8 0 / 1
+    host array of length `n` (from a bool sequence / numpy array / tensor)."""
+    if value is None or isinstance(value, (bool, int, str)) or np.ndim(value) == 0:
+        return bool(value)  # (None, numbers and 0-d arrays / tensors included: one choice, by truth value as ever)
+    host = value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else np.asarray(value)
+    if host.dtype != np.bool_ and not (host.dtype.kind in "iu" and host.size and int(host.min()) >= 0 and int(host.max()) <= 1):
+        raise ValueError(f"{name} must be a bool or a bool sequence / array / tensor of length num_envs")
+    if host.shape != (n,):
+        raise ValueError(f"{name}: expected one value per game ({n}), got shape {tuple(host.shape)}")
+    return host.astype(np.uint8)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
@@ -141,6 +154,15 @@ class raw_env(ParallelEnv):
     ``sprite_dir`` -- the reference's ``pikazoo/env/img`` directory, found by itself when the reference
     package is installed -- or from a ready ``sprites`` set, see :mod:`pikazoo_amd.render`; there is no
     "human" window).
+
+    Per-game computer players: ``is_player1_computer`` / ``is_player2_computer`` also take one bool per game (a sequence,
+    numpy array or tensor of length ``num_envs``).  The env is then MIXED: game i is, frame by frame, the reference env
+    constructed with its two flags.  The roles live in ``computer_players`` (``uint8[num_envs]`` on the device: bit 0
+    = player 1 is the computer, bit 1 = player 2), :meth:`set_computer_players` rewrites them between steps, and
+    ``state_dict`` carries them.  ``step`` takes both agents' actions for every game, as the reference does with a
+    computer player; every wrapper, state format, observation and action dtype, ``auto_reset``, ``output_ring``,
+    ``reset(mask=)`` and graph capture work as on any env.  ``frame_skip > 1``, ``step_random``, ``rollout_random``,
+    ``step_many`` and the held launches raise ``ValueError`` on a mixed env.  Two Python bools: one choice for the batch.
 
     Batched-env kwargs: ``num_envs``; ``device`` (a CUDA/HIP device); ``seed`` (Philox key of
     the env RNG stream -- the reference seeds PCG64 from OS entropy and ignores ``reset(seed)``,
@@ -272,8 +294,22 @@ class raw_env(ParallelEnv):
         cfg = _native.PzConfig()
         cfg.winning_score = self.winning_score
         cfg.serve_mode = _native.SERVE_MODES[serve]
-        cfg.p1_computer = int(bool(is_player1_computer))
-        cfg.p2_computer = int(bool(is_player2_computer))
+        # who plays: two Python bools are one choice for the batch (the configuration's two flags, today's kernels); a
+        # per-game value for either side makes the env MIXED -- one uint8 role code per game on the device (bit 0:
+        # player 1 is the computer, bit 1: player 2), read by every step launch (pz_step_mixed; cfg's flags are ignored)
+        roles1 = _per_game_roles(is_player1_computer, self.num_envs, "is_player1_computer")
+        roles2 = _per_game_roles(is_player2_computer, self.num_envs, "is_player2_computer")
+        self._mixed = not (isinstance(roles1, bool) and isinstance(roles2, bool))
+        self.computer_players = None
+        if self._mixed:
+            if self.frame_skip > 1:
+                raise ValueError("a mixed env (per-game is_player1_computer / is_player2_computer) steps single frames: "
+                                 f"frame_skip={self.frame_skip} needs one choice of players for the whole batch")
+            codes = np.zeros(self.num_envs, dtype=np.uint8) + np.uint8(1) * roles1 + np.uint8(2) * roles2
+            self.computer_players = torch.as_tensor(codes.astype(np.uint8), device=self.device)
+            roles1 = roles2 = False
+        cfg.p1_computer = int(roles1)
+        cfg.p2_computer = int(roles2)
         cfg.simplify_action = 0
         cfg.ballpos_reward = 0
         cfg.x_line, cfg.y_line = 216, 176
@@ -303,7 +339,7 @@ class raw_env(ParallelEnv):
         self._a1_seen = self._a2_seen = (lambda: None, 0, None, 0)
         self._tables = None
         self._tables_ref = None  # `const pz_flight_tables*` of every step call (None: compute in the kernel)
-        computer = bool(cfg.p1_computer or cfg.p2_computer)
+        computer = bool(cfg.p1_computer or cfg.p2_computer) or self._mixed  # (a mixed env: as one with a computer player)
         self.flight_tables = "none"
         if computer and any(_TABLE_MODES[flight_tables]):
             self.flight_tables = "both" if all(_TABLE_MODES[flight_tables]) else "power_hit"
@@ -798,6 +834,8 @@ class raw_env(ParallelEnv):
         out = self._out
         if self.frame_skip > 1:
             self._step_held(out, p1, p2, f1)
+        elif self._mixed:
+            self._step_mixed(out, p1, p2, f1)
         else:
             # pz_step through its prepared-argument form: one FFI call with four scalars (the twelve buffers and the
             # configuration were bound once) -- the host side of a step stays below the duration of the launch it issues
@@ -838,6 +876,47 @@ class raw_env(ParallelEnv):
             self._cfg.action_format = 0
         if rc:
             _native.check(rc, "pz_step_held")
+
+    def _step_mixed(self, out, p1, p2, fmt):
+        """A mixed env's frame: who plays is read per game from ``computer_players`` (``pz_step_mixed``)."""
+        p = out.ptrs
+        self._cfg.action_format = fmt  # (the launch copies the configuration; every other call takes int32)
+        try:
+            with torch.cuda.device(self.device):
+                rc = self._lib.pz_step_mixed(p[0], self.num_envs, self._stride, self._cfg_ref, self.computer_players.data_ptr(),
+                                             p1, p2, p[1], p[2], p[3], p[4], p[5], self._stats_ptr(), self._tables_ref,
+                                             self._stream())
+        finally:
+            self._cfg.action_format = 0
+        if rc:
+            _native.check(rc, "pz_step_mixed")
+
+    def set_computer_players(self, player_1=None, player_2=None):
+        """Rewrite who plays in a mixed env, between steps: per side ``None`` (keep), a bool (every game) or one bool per
+        game (sequence / array / tensor).  The role codes are rewritten in place on the caller's stream -- no
+        synchronisation, and a captured graph of ``step`` reads the new roles on its next replay.  A game whose role
+        changes continues from its state: its later frames are the reference game's with ``player.is_computer`` flipped
+        at this frame."""
+        if not self._mixed:
+            raise ValueError("set_computer_players needs a mixed env: construct it with a per-game is_player1_computer / "
+                             "is_player2_computer (a bool sequence of length num_envs)")
+        for bit, value, name in ((1, player_1, "player_1"), (2, player_2, "player_2")):
+            if value is None:
+                continue
+            if isinstance(value, torch.Tensor) and value.device == self.device and value.dtype == torch.bool:
+                if tuple(value.shape) != (self.num_envs,):
+                    raise ValueError(f"{name}: expected one value per game ({self.num_envs}), got shape {tuple(value.shape)}")
+                on = value
+            else:
+                roles = _per_game_roles(value, self.num_envs, name)
+                on = torch.full((self.num_envs,), roles, dtype=torch.bool, device=self.device) if isinstance(roles, bool) \
+                    else torch.as_tensor(roles, device=self.device).bool()
+            self.computer_players.bitwise_and_(3 ^ bit).bitwise_or_(on.to(torch.uint8) * bit)
+
+    def _no_mixed(self, what: str):
+        if self._mixed:
+            raise ValueError(f"{what} takes one choice of players for the whole batch; this is a mixed env (per-game "
+                             "is_player1_computer / is_player2_computer), which steps single frames through step()")
 
     def _no_frame_skip(self, what: str):
         if self.frame_skip > 1:
@@ -881,6 +960,7 @@ class raw_env(ParallelEnv):
         ``action_seed``, step indices ``t0 .. t0+k-1``; ``t0`` defaults to ``steps_done``) in ONE
         launch.  Returns the last frame's step tuple."""
         self._no_frame_skip("step_random")
+        self._no_mixed("step_random")
         self._no_unfused_wrappers("step_random")
         if t0 is None:
             t0 = self.steps_done
@@ -919,6 +999,7 @@ class raw_env(ParallelEnv):
         return self._rollout_random("rollout_random_held", action_seed, k, t0, out)
 
     def _rollout_random(self, what, action_seed, k, t0, out):
+        self._no_mixed(what)
         self._no_unfused_wrappers(what)
         if t0 is None:
             t0 = self.steps_done
@@ -968,6 +1049,7 @@ class raw_env(ParallelEnv):
         return self._step_many("step_many_held", actions, out)
 
     def _step_many(self, what, actions, out):
+        self._no_mixed(what)
         self._no_unfused_wrappers(what)
         n, dev = self.num_envs, self.device
         if actions.dim() != 3 or actions.shape[1] != 2 or actions.shape[2] != n:
@@ -1102,6 +1184,7 @@ class raw_env(ParallelEnv):
                 "env_id_base": self.env_id_base, "config": self._cfg_dict(),
                 "episode_stats": None if self._stats is None else self._stats.clone(),
                 "episodes_done": self._episodes.clone(),
+                "computer_players": None if not self._mixed else self.computer_players.clone(),
                 "scenery": None if self._scenery is None else self._scenery[:, :self.num_envs].clone()}
 
     def load_state_dict(self, sd):
@@ -1121,6 +1204,10 @@ class raw_env(ParallelEnv):
             raise ValueError("checkpoint was taken with another seed / env_id_base")
         elif self.frame_skip != 1:
             raise ValueError(f"checkpoint was taken with frame_skip=1 (it names none), this env has frame_skip={self.frame_skip}")
+        roles = sd.get("computer_players")  # (a uniform env's checkpoint carries none, as every one from before mixed envs)
+        if (roles is None) != (not self._mixed):
+            raise ValueError("checkpoint and env disagree on per-game computer players (a mixed env's checkpoint carries "
+                             "its role codes, a uniform env's none)")
         stats = sd.get("episode_stats")
         if (stats is None) != (self._stats is None):
             raise ValueError("checkpoint and env disagree on RecordEpisodeStatistics")
@@ -1134,6 +1221,8 @@ class raw_env(ParallelEnv):
             self._stats.copy_(stats)
         if sd.get("episodes_done") is not None:
             self._episodes.copy_(sd["episodes_done"])
+        if roles is not None:
+            self.computer_players.copy_(roles)
         self.steps_done = int(sd["steps_done"])
         self.agents = self.possible_agents[:]
 
