@@ -93,7 +93,11 @@ def main():
     viewer.step_random(action_seed=3, k=200)
     frames = viewer.render(lanes=[0, 1, 2, 3])
     print("render:", tuple(frames.shape), frames.dtype, "(reference sprites)" if img_dir else "(synthetic sprites)")
-
+    # pixel observations: the same screen grey and 4 x downsampled in one launch, 8 208 bytes per game (an env without
+    # scenery: an observation must not advance the env RNG)
+    plain = pikazoo_v0.env(num_envs=1024, device="cuda:0", seed=0, render_mode="rgb_array", sprites=sprites)
+    screens = plain.render_observations(4, lanes=[0, 1, 2, 3])
+    print("pixel observations:", tuple(screens.shape), screens.dtype)
 
 if __name__ == "__main__":
     main()

@@ -455,6 +455,23 @@ int pz_render(int32_t *state, int64_t n, int64_t stride, const pz_config *cfg, c
               const uint32_t *atlas, const pz_sprite *sprites, const uint32_t *background,
               int32_t *scenery, uint8_t *frames, void *stream);
 
+/* ---- pixel observations: grey, box-filtered frames -------------------------------------------
+ * The frame pz_render draws with scenery == NULL (background, players, shadows, ball / hyper ball / trail, score
+ * boards; blended in RGB per full-resolution pixel, in draw order), then per full-resolution pixel
+ * y = (77 R + 150 G + 29 B + 128) >> 8 and per output pixel (r, c) the mean of y over the scale x scale block at
+ * (r * scale, c * scale): (sum + scale * scale / 2) >> (2 log2 scale).  Integer arithmetic throughout: bit-exact.
+ * uint8[m][304 / scale][432 / scale] for the games `lanes` (NULL: games 0..m-1, m <= n), game j's frame at
+ * frames + j * frame_stride -- a caller can write one slot of a frame stack.  scale in {1, 2, 4, 8}, else PZ_E_CONFIG;
+ * frames (and background_gray) 4-byte aligned and frame_stride a multiple of 4, else PZ_E_ALIGN; frame_stride >= the
+ * frame's bytes, else PZ_E_SIZE; m == 0: no launch.  A lane outside 0..n-1 leaves its frame unwritten.
+ * background_gray: uint8[304 / scale][432 / scale], the same reduction of `background` alone (the caller computes it
+ * once per sprite set and scale); output pixels no sprite touches are looked up there.  May be NULL: every pixel is
+ * composed, with the same result.  Reads int32 state columns only and writes nothing but `frames`. */
+int pz_render_gray(const int32_t *state, int64_t n, int64_t stride, const int32_t *lanes, int64_t m,
+                   const uint32_t *atlas, const pz_sprite *sprites, const uint32_t *background,
+                   const uint8_t *background_gray, int32_t scale, uint8_t *frames, int64_t frame_stride,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2723,6 +2723,171 @@ static int launch_mixed(const StepArgs& a, const uint8_t* computer_mask, hipStre
 
 }  // namespace pz_mixed
 
+// ---- pixel observations: grey, box-filtered frames of the state (pz_render_gray) ------------------------------------
+// The frame render_kernel draws without scenery, reduced per full-resolution pixel to luma
+// y = (77 R + 150 G + 29 B + 128) >> 8 after the last blit, then averaged over scale x scale blocks
+// ((sum + scale^2 / 2) >> 2 log2 scale): uint8[304 / scale][432 / scale] per game, in integer arithmetic
+// throughout.  The RGB frame is never materialised: a thread composes the full-resolution pixels of its output pixels in
+// registers and stores one dword (four output bytes in frame-linear order -- at scale 8 a 54-byte row is no whole
+// number of dwords, the 2 052-byte frame is).  One block per game (more at scales 1 and 2, blockIdx.y), looping over the
+// frame's dwords: the draw list is resolved once per block -- twelve rectangles with their atlas offsets, in LDS.  The
+// rectangle tests read them at wave-uniform addresses; the blend loop of a composed pixel indexes them by the pixel's
+// own slot mask (per thread).  The composing loops are not unrolled and run per thread: at scale 8 one thread walks
+// 4 x 64 full-resolution pixels while the background lanes of its wave wait, and one block covers a game's 513 dwords
+// (spreading composed blocks over lanes is the lever if the composing path dominates).  An output block that no rectangle intersects is the grey background, looked up in
+// `background_gray` (a dword for four such neighbours); with background_gray == NULL it is composed like every other.
+// A namespace of its own, as pz_mixed: the pz:: kernels of the code object are the swept 177.
+namespace pz_pixels {
+using namespace pz;
+
+struct Rect {  // one resolved draw-list slot (width == 0: not drawn)
+    int x0, y0, width, height, offset, mirrored, pad0, pad1;
+};
+
+constexpr int kThreads = 256;
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void gray_kernel(const int32_t* __restrict__ state, int64_t n, int64_t stride,
+                                                        const int32_t* __restrict__ lanes, const uint32_t* __restrict__ atlas,
+                                                        const pz_sprite* __restrict__ sprites,
+                                                        const uint32_t* __restrict__ background,
+                                                        const uint8_t* __restrict__ background_gray,
+                                                        uint8_t* __restrict__ frames, int64_t frame_stride)
+{
+    constexpr int kW = PZ_FRAME_WIDTH / S, kH = PZ_FRAME_HEIGHT / S;
+    constexpr int kDwords = kW * kH / 4;
+    constexpr int kShift = S == 1 ? 0 : (S == 2 ? 2 : (S == 4 ? 4 : 6));
+    static_assert(S == 1 || S == 2 || S == 4 || S == 8, "scale");
+    static_assert((kW * kH) % 4 == 0, "a frame is a whole number of dwords");
+    __shared__ __attribute__((aligned(16))) Rect rects[12];
+
+    const int64_t game = lanes != nullptr ? (int64_t)lanes[blockIdx.x] : (int64_t)blockIdx.x;  // block-uniform
+    if (game < 0 || game >= n) return;
+    auto word = [&](int f) { return state[(int64_t)f * stride + game]; };
+
+    // TWIN of render_kernel's draw list (its instruction stream is pinned, so the twenty lines are repeated here): the
+    // order of raw_env.draw (:250-255), twelve fixed slots (sprite < 0: not drawn).  A change there belongs here too.
+    Blit list[12];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {  // draw_player :257-275
+        const int c0 = p * PZ_P_WORDS;
+        const int st = word(c0 + PZ_P_STATE), fr = word(c0 + PZ_P_FRAME_NUMBER), dive = word(c0 + PZ_P_DIVING_DIRECTION);
+        const int idx = st < 4 ? 5 * st + fr : (st == 4 ? 17 + fr : 18 + 5 * (st - 5) + fr);  // :63-68
+        const bool diving = st == 3 || st == 4;
+        const bool flip = p == 0 ? (diving && dive == -1) : !(diving && dive == 1);  // :263-264
+        list[p] = Blit{PZ_SPRITE_PIKACHU + min(max(idx, 0), 27), word(c0 + PZ_P_X), word(c0 + PZ_P_Y), flip ? 3 : 1};
+    }
+    list[2] = Blit{PZ_SPRITE_SHADOW, word(PZ_P_X), 273, 1};                     // :277-278
+    list[3] = Blit{PZ_SPRITE_SHADOW, word(PZ_P_WORDS + PZ_P_X), 273, 1};
+    const int rotation = min(max(word(PZ_B_FINE_ROTATION) / 10, 0), 5);         // physics.py:388
+    list[4] = Blit{PZ_SPRITE_BALL + rotation, word(PZ_B_X), word(PZ_B_Y), 1};   // draw_ball :282-290
+    list[5] = Blit{PZ_SPRITE_SHADOW, word(PZ_B_X), 273, 1};
+    const bool power = word(PZ_B_IS_POWER_HIT) != 0;
+    list[6] = Blit{power ? PZ_SPRITE_BALL_HYPER : -1, word(PZ_B_PREVIOUS_X), word(PZ_B_PREVIOUS_Y), 1};
+    list[7] = Blit{power ? PZ_SPRITE_BALL_TRAIL : -1, word(PZ_B_PREVIOUS_PREVIOUS_X), word(PZ_B_PREVIOUS_PREVIOUS_Y), 1};
+    const int s1 = word(PZ_E_SCORE_P1), s2 = word(PZ_E_SCORE_P2);                // :327-336 (top-left blits)
+    list[8] = Blit{s1 >= 10 ? PZ_SPRITE_NUMBER + 1 : -1, 14, 10, 0};
+    list[9] = Blit{PZ_SPRITE_NUMBER + s1 % 10, 14 + 32, 10, 0};
+    list[10] = Blit{s2 >= 10 ? PZ_SPRITE_NUMBER + 1 : -1, PZ_FRAME_WIDTH - 32 - 32 - 14, 10, 0};
+    list[11] = Blit{PZ_SPRITE_NUMBER + s2 % 10, PZ_FRAME_WIDTH - 32 - 32 - 14 + 32, 10, 0};
+
+    // thread b resolves slot b (the list is block-uniform; the static loop keeps it out of scratch)
+#pragma unroll
+    for (int b = 0; b < 12; ++b) {
+        if ((int)threadIdx.x == b) {
+            Rect r{0, 0, 0, 0, 0, 0, 0, 0};
+            const Blit bl = list[b];
+            if (bl.sprite >= 0) {
+                const pz_sprite sp = sprites[min(bl.sprite, PZ_SPRITE_COUNT - 1)];
+                const bool centred = (bl.flip & 1) != 0;
+                r.x0 = centred ? bl.x0 - sp.width / 2 : bl.x0;    // blit_center :40-43
+                r.y0 = centred ? bl.y0 - sp.height / 2 : bl.y0;
+                r.width = sp.width;
+                r.height = sp.height;
+                r.offset = sp.offset;
+                r.mirrored = (bl.flip & 2) != 0 ? 1 : 0;
+            }
+            rects[b] = r;
+        }
+    }
+    __syncthreads();
+
+    // slots whose rectangle meets the full-resolution pixels [bx0, bx1) x [by0, by1); 64-bit: a planted coordinate
+    // near the int32 limits must not wrap into the frame
+    auto slots_meeting = [&](int bx0, int by0, int bx1, int by1) {
+        uint32_t mask = 0u;
+#pragma unroll
+        for (int b = 0; b < 12; ++b) {
+            const int4 r = *reinterpret_cast<const int4*>(&rects[b]);  // x0, y0, width, height
+            const bool hit = (int64_t)r.x < bx1 && (int64_t)r.x + r.z > bx0 && (int64_t)r.y < by1 && (int64_t)r.y + r.w > by0;
+            mask |= hit ? 1u << b : 0u;
+        }
+        return mask;
+    };
+
+    uint8_t* const frame = frames + (int64_t)blockIdx.x * frame_stride;
+    for (int d = (int)(blockIdx.y * kThreads + threadIdx.x); d < kDwords; d += (int)(gridDim.y * kThreads)) {
+        const int p0 = 4 * d;                      // first of the thread's four output pixels, frame-linear
+        const int r0 = p0 / kW, r3 = (p0 + 3) / kW;  // (they share a row unless S == 8)
+        const int c0 = p0 - r0 * kW;
+        // the four pixels' bounding box: their columns in one row, whole rows when they span two
+        const uint32_t near = r0 == r3 ? slots_meeting(c0 * S, r0 * S, (c0 + 4) * S, (r0 + 1) * S)
+                                       : slots_meeting(0, r0 * S, PZ_FRAME_WIDTH, (r3 + 1) * S);
+        uint32_t packed;
+        if (near == 0u && background_gray != nullptr) {
+            packed = *reinterpret_cast<const uint32_t*>(background_gray + p0);
+        } else {
+            packed = 0u;
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) {
+                const int p = p0 + k;
+                const int row = p / kW, col = p - row * kW;
+                const int x0 = col * S, y0 = row * S;
+                const uint32_t mask = near != 0u ? slots_meeting(x0, y0, x0 + S, y0 + S) : 0u;
+                uint32_t value;
+                if (mask == 0u && background_gray != nullptr) {
+                    value = background_gray[p];
+                } else {
+                    uint32_t sum = 0u;
+#pragma unroll 1
+                    for (int dy = 0; dy < S; ++dy) {
+#pragma unroll 1
+                        for (int dx = 0; dx < S; ++dx) {
+                            const int x = x0 + dx, y = y0 + dy;
+                            uint32_t px = background[y * PZ_FRAME_WIDTH + x];
+                            for (uint32_t m = mask; m != 0u; m &= m - 1u) {  // ascending: the draw order
+                                const Rect r = rects[__ffs((int)m) - 1];
+                                const int sx = x - r.x0, sy = y - r.y0;
+                                if ((unsigned)sx < (unsigned)r.width && (unsigned)sy < (unsigned)r.height)
+                                    px = blend_over(px, atlas[r.offset + sy * r.width + (r.mirrored ? r.width - 1 - sx : sx)]);
+                            }
+                            sum += (77u * (px & 0xFFu) + 150u * ((px >> 8) & 0xFFu) + 29u * ((px >> 16) & 0xFFu) + 128u) >> 8;
+                        }
+                    }
+                    value = (sum + (uint32_t)(S * S / 2)) >> kShift;
+                }
+                packed |= value << (8 * k);
+            }
+        }
+        *reinterpret_cast<uint32_t*>(frame + p0) = packed;
+    }
+}
+
+// blocks per game: the frame's dwords in about eight passes of a block at every scale
+template <int S>
+static void launch_gray(const int32_t* state, int64_t n, int64_t stride, const int32_t* lanes, int64_t m, const uint32_t* atlas,
+                        const pz_sprite* sprites, const uint32_t* background, const uint8_t* background_gray, uint8_t* frames,
+                        int64_t frame_stride, hipStream_t stream)
+{
+    constexpr int kDwords = (PZ_FRAME_WIDTH / S) * (PZ_FRAME_HEIGHT / S) / 4;
+    constexpr int kBlocks = S == 1 ? 16 : (S == 2 ? 4 : 1);
+    static_assert(kDwords > 0 && kBlocks >= 1, "grid");
+    hipLaunchKernelGGL(gray_kernel<S>, dim3((unsigned int)m, kBlocks), dim3(kThreads), 0, stream, state, n, stride, lanes, atlas,
+                       sprites, background, background_gray, frames, frame_stride);
+}
+
+}  // namespace pz_pixels
+
 using namespace pz;
 
 extern "C" {
@@ -3085,6 +3250,29 @@ int pz_render(int32_t* state, int64_t n, int64_t stride, const pz_config* cfg, c
                            state, n, stride, *cfg, lanes, m);
     hipLaunchKernelGGL(render_kernel, grid, dim3(256), 0, (hipStream_t)stream, state, n, stride, lanes, atlas, sprites,
                        background, scenery, frames);
+    return (int)hipGetLastError();
+}
+
+int pz_render_gray(const int32_t* state, int64_t n, int64_t stride, const int32_t* lanes, int64_t m, const uint32_t* atlas,
+                   const pz_sprite* sprites, const uint32_t* background, const uint8_t* background_gray, int32_t scale,
+                   uint8_t* frames, int64_t frame_stride, void* stream)
+{
+    if (!state || !atlas || !sprites || !background || !frames) return PZ_E_NULL;
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return PZ_E_CONFIG;
+    if (n < 0 || stride < n || stride > kMaxLanesPerLaunch || m < 0 || m > 0x7FFFFFFF || (lanes == nullptr && m > n))
+        return PZ_E_SIZE;
+    if (((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(background_gray)) & 3u) != 0 ||
+        (frame_stride & 3) != 0)
+        return PZ_E_ALIGN;
+    if (frame_stride < (int64_t)(PZ_FRAME_WIDTH / scale) * (PZ_FRAME_HEIGHT / scale)) return PZ_E_SIZE;
+    if (m == 0) return PZ_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    switch (scale) {
+    case 1: pz_pixels::launch_gray<1>(state, n, stride, lanes, m, atlas, sprites, background, background_gray, frames, frame_stride, s); break;
+    case 2: pz_pixels::launch_gray<2>(state, n, stride, lanes, m, atlas, sprites, background, background_gray, frames, frame_stride, s); break;
+    case 4: pz_pixels::launch_gray<4>(state, n, stride, lanes, m, atlas, sprites, background, background_gray, frames, frame_stride, s); break;
+    default: pz_pixels::launch_gray<8>(state, n, stride, lanes, m, atlas, sprites, background, background_gray, frames, frame_stride, s); break;
+    }
     return (int)hipGetLastError();
 }
 

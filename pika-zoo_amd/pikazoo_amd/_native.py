@@ -105,6 +105,8 @@ _SIGNATURES = {
     "pz_scenery_track": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(PzConfig), C.c_int32, _P]),
     # (cfg may be None when no scenery is passed: ctypes passes NULL for None)
     "pz_render": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(PzConfig), _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    # (state, n, stride, lanes, m, atlas, sprites, background, background_gray or None, scale, frames, frame_stride, stream)
+    "pz_render_gray": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -1267,6 +1267,45 @@ class raw_env(ParallelEnv):
                                         self._sprites, lane_t, self._stream(), out)
         return frames[0].cpu().numpy() if self.scalar_api else frames
 
+    def render_observations(self, scale: int = 4, lanes=None, out: Optional[torch.Tensor] = None):
+        """Pixel observations of the current state: the frame ``render()`` draws, as grey ``uint8[m, 304 // scale,
+        432 // scale]`` on the device (``pz_render_gray``: luma ``(77 R + 150 G + 29 B + 128) >> 8`` per pixel after the
+        last blit, then the rounded mean over scale x scale blocks; one launch, the RGB frame is never stored).
+        `scale` in {1, 2, 4, 8}; `lanes` as for ``render()`` (default: every game, as long as the result stays below
+        1 GiB); `out`: a uint8 view of that shape on the env's device whose frames are contiguous, 4-byte aligned and
+        a multiple of 4 bytes apart, e.g. slot ``big[:, j]`` of a ``uint8[m, stack, h, w]`` frame stack.  An observation
+        must not change the game: a ``scenery=True`` env, whose clouds and waves are drawn from the env RNG, is refused.
+        With ``lanes=None``, `out` given and the int32 state format the call does not synchronise (it can be captured
+        into a graph).  ``scalar_api`` envs get a numpy ``[h, w]`` array."""
+        from . import render as _render
+
+        if self.render_mode is None:
+            raise ValueError('render_observations needs render_mode="rgb_array"')
+        if self._scenery is not None:
+            raise ValueError("render_observations on a scenery=True env: the clouds and waves are drawn from the env RNG, "
+                             "and an observation must not change the game")
+        scale = _render.gray_scale(scale)
+        if self._sprites is None:
+            d = self._sprite_dir or _render.default_image_dir()
+            if d is None:
+                raise FileNotFoundError(
+                    "render_observations needs the reference's sprites: pass sprite_dir=<.../pikazoo/env/img> (or "
+                    "sprites=) to the env; they are not redistributed with this package")
+            self._sprites = _render.load_sprites(d, self.device)
+        lane_t = None
+        if lanes is not None:
+            lane_t = torch.as_tensor(lanes, device=self.device).reshape(-1).to(torch.int32).contiguous()
+            if lane_t.numel() and (int(lane_t.min()) < 0 or int(lane_t.max()) >= self.num_envs):
+                raise IndexError("lane out of range")
+        m = self.num_envs if lane_t is None else int(lane_t.numel())
+        if out is None and m * (_render.HEIGHT // scale) * (_render.WIDTH // scale) > (1 << 30):
+            raise ValueError(f"the observations of {m} games at scale {scale} need more than 1 GiB: pass lanes= or out=")
+        with torch.cuda.device(self.device):
+            cols = self._state_buf if self._state_view is not None else self._unpacked()[0]  # (kept alive over the launch)
+            frames = _render.render_gray(self._lib, cols.data_ptr(), self.device, self.num_envs, self._stride,
+                                         self._sprites, lane_t, self._stream(), scale, out)  # (checks `out` before the launch)
+        return frames[0].cpu().numpy() if self.scalar_api else frames
+
     def close(self):
         pass
 

@@ -173,6 +173,34 @@ class SpriteSet:
         self.atlas = torch.from_numpy(packed.view(np.int32).copy()).to(self.device)
         self.background = torch.from_numpy(bg_packed.view(np.int32).copy()).to(self.device)
         self.table = torch.from_numpy(np.frombuffer(bytes(table), np.int32).copy()).to(self.device)
+        self._background_gray = {}
+
+    def background_gray(self, scale: int) -> torch.Tensor:
+        """uint8 ``[304 // scale, 432 // scale]`` on the device: the grey, box-filtered background (what
+        ``pz_render_gray`` looks up where no sprite is drawn), computed once per scale."""
+        if scale not in self._background_gray:
+            self._background_gray[scale] = torch.from_numpy(gray_downsample(self.background_host, scale)).to(self.device)
+        return self._background_gray[scale]
+
+
+GRAY_SCALES = (1, 2, 4, 8)
+
+
+def gray_scale(scale) -> int:
+    """`scale` as a Python int if it is an integer in GRAY_SCALES (no bool, no 2.0), else ValueError."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in GRAY_SCALES:
+        raise ValueError(f"scale must be one of the integers {GRAY_SCALES}, got {scale!r}")
+    return int(scale)
+
+
+def gray_downsample(frame_rgb: np.ndarray, scale: int) -> np.ndarray:
+    """uint8 ``[..., 304 // scale, 432 // scale]`` of uint8 ``[..., 304, 432, 3]``: luma ``(77 R + 150 G + 29 B + 128)
+    >> 8`` per pixel, then the rounded mean over scale x scale blocks (the definition ``pz_render_gray`` computes)."""
+    f = frame_rgb.astype(np.int64)
+    y = (77 * f[..., 0] + 150 * f[..., 1] + 29 * f[..., 2] + 128) >> 8
+    h, w = y.shape[-2:]
+    blocks = y.reshape(*y.shape[:-2], h // scale, scale, w // scale, scale).sum(axis=(-3, -1))
+    return ((blocks + scale * scale // 2) // (scale * scale)).astype(np.uint8)
 
 
 def default_image_dir() -> Optional[Path]:
@@ -238,4 +266,36 @@ def render(lib, state_ptr: int, device, n: int, stride: int, sprite_set: SpriteS
                                 sprite_set.atlas.data_ptr(), sprite_set.table.data_ptr(),
                                 sprite_set.background.data_ptr(), None if scenery is None else scenery.data_ptr(),
                                 out.data_ptr(), stream), "pz_render")
+    return out
+
+
+def check_gray_out(out, m: int, scale: int, device) -> None:
+    """``render_observations(out=)``: the kernel writes each game's frame as dwords at ``out.data_ptr() + j *
+    out.stride(0)``, so anything but such a view on this device would be overrun or torn silently."""
+    h, w = HEIGHT // scale, WIDTH // scale
+    ok = isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == (m, h, w) \
+        and out.device == torch.device(device) and out.stride(2) == 1 and out.stride(1) == w \
+        and out.stride(0) % 4 == 0 and out.stride(0) >= h * w and out.data_ptr() % 4 == 0
+    if not ok:
+        raise ValueError(f"render_observations(out=): need a uint8 view of shape {(m, h, w)} on {device} whose frames are "
+                         f"contiguous, 4-byte aligned and a multiple of 4 bytes apart, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} strides "
+                         f"{tuple(out.stride()) if isinstance(out, torch.Tensor) else None} on {getattr(out, 'device', None)}")
+
+
+def render_gray(lib, state_ptr: int, device, n: int, stride: int, sprite_set: SpriteSet, lanes: Optional[torch.Tensor],
+                stream: int, scale: int, out: Optional[torch.Tensor] = None, fast_path: bool = True) -> torch.Tensor:
+    """uint8 ``[m, 304 // scale, 432 // scale]`` grey frames of the games `lanes` (None: all n) through
+    ``pz_render_gray``; `state_ptr` = the ``int32[44, stride]`` columns on `device`.  Nothing here synchronises."""
+    m = n if lanes is None else int(lanes.numel())
+    h, w = HEIGHT // scale, WIDTH // scale
+    if out is None:
+        out = torch.empty((m, h, w), dtype=torch.uint8, device=device)
+    else:
+        check_gray_out(out, m, scale, device)
+    _native.check(lib.pz_render_gray(state_ptr, n, stride, None if lanes is None else lanes.data_ptr(), m,
+                                     sprite_set.atlas.data_ptr(), sprite_set.table.data_ptr(),
+                                     sprite_set.background.data_ptr(),
+                                     sprite_set.background_gray(scale).data_ptr() if fast_path else None, scale,
+                                     out.data_ptr(), out.stride(0), stream), "pz_render_gray")
     return out
