@@ -61,6 +61,16 @@ def main():
     print(f"rollout_random: {n * 32 * 50 / (time.perf_counter() - t0) / 1e9:.2f} G env-steps/s; "
           f"trajectory obs {tuple(out['obs']['player_1'].shape)}")
 
+    # what an actor-critic trainer does first with that trajectory: GAE(gamma, lambda) advantages and returns, both agents
+    # in ONE launch (pikazoo_amd.learn, a library of its own).  The values would come from the critic on out["obs"] plus
+    # the observation after the last step (row k, the bootstrap); float16 / bfloat16 values are read as they are
+    values = {agent: torch.randn(32 + 1, n, device="cuda:0") for agent in env.agents}
+    targets = raw.gae(out, values, gamma=0.99, lam=0.95)
+    targets = raw.gae(out, values, gamma=0.99, lam=0.95, out=targets)  # (reuses the buffers: no allocation, capturable)
+    torch.cuda.synchronize()
+    print("gae: advantages", tuple(targets["advantages"]["player_1"].shape), targets["advantages"]["player_1"].dtype,
+          "| returns", tuple(targets["returns"]["player_2"].shape))
+
     # a larger batch in the packed state format (36 instead of 176 bytes of state per game; same results) and with int16
     # observations (same values, half the bytes): this is where the step launch streams HBM, and fewer bytes are less time
     for fmt, odt in (("int32", torch.int32), ("packed", torch.int32), ("packed", torch.int16)):

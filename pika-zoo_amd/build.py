@@ -1,11 +1,14 @@
-"""Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so -- for gfx950 with hipcc (in-tree, no JIT cache).
+"""Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so and libpikazoo_learn.so -- for gfx950 with hipcc (in-tree, no
+JIT cache).
 
     python pika-zoo_amd/build.py [--force]
 
 The product library is plain HIP + a C ABI (include/pikazoo_hip.h); it links only against the
 HIP runtime, not against torch.  hipcc cross-compiles without a GPU present.  The diagnostics library
 (include/pikazoo_diag.h: pz_probe_launch, pz_selftest_predictor) is compiled from the product's own headers and is
-loaded by bench.py and tests/ only (pika-zoo_amd/diag.py); it carries the same build id.
+loaded by bench.py and tests/ only (pika-zoo_amd/diag.py); it carries the same build id.  The learning library
+(include/pikazoo_learn.h: pz_gae) is a third translation unit with kernels of its own, bound by pikazoo_amd/learn.py; the
+product library holds none of it.  The three compiles are independent and run side by side.
 """
 from __future__ import annotations
 
@@ -23,10 +26,12 @@ INCLUDE = REPO / "include"
 LIB_DIR = PKG_ROOT / "lib"
 LIB = LIB_DIR / "libpikazoo_hip.so"
 DIAG_LIB = LIB_DIR / "libpikazoo_diag.so"
+LEARN_LIB = LIB_DIR / "libpikazoo_learn.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
-DEPS = SOURCES + DIAG_SOURCES + [CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp",
-                                 CSRC / "pz_dispatch.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h"]
+LEARN_SOURCES = [CSRC / "pz_learn.hip"]
+DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + [CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp",
+                                 CSRC / "pz_dispatch.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
@@ -69,7 +74,7 @@ def library_id(lib: Path = LIB):
 
 
 def needs_build() -> bool:
-    return library_id() != source_id() or library_id(DIAG_LIB) != source_id()
+    return any(library_id(lib) != source_id() for lib in (LIB, DIAG_LIB, LEARN_LIB))
 
 
 def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
@@ -84,17 +89,25 @@ def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
-    """The product library (returned) and the diagnostics library beside it (a few seconds)."""
+    """The product library (returned) with the diagnostics and the learning library beside it: each is compiled when it
+    is missing or stale, the compiles side by side (a cold build takes about as long as the product library alone: some
+    three minutes; an up-to-date tree costs three file reads)."""
     if any("PZ_DIAGNOSTIC_BUILD" in f for f in extra_flags):
         # csrc/pz_diagnostic.hpp: the one compile-time switch of the kernels -- tools/ab.py builds such variants into
         # tools/bin/; the product path never holds one (and _native.load() would refuse its build id "diagnostic")
         raise ValueError("a diagnostic build (-DPZ_DIAGNOSTIC_BUILD) is never written to the product library's path")
     want = source_id(tuple(extra_flags))
     LIB_DIR.mkdir(parents=True, exist_ok=True)
-    if force or extra_flags or library_id(DIAG_LIB) != want:
-        _compile(DIAG_LIB, DIAG_SOURCES, extra_flags, verbose)
-    if force or extra_flags or library_id() != want:
-        _compile(LIB, SOURCES, extra_flags, verbose)
+    todo = [(out, sources) for out, sources in ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES))
+            if force or extra_flags or library_id(out) != want]
+    if len(todo) > 1:
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(len(todo)) as pool:  # (the threads only wait for their hipcc)
+            for done in [pool.submit(_compile, out, sources, extra_flags, verbose) for out, sources in todo]:
+                done.result()
+    elif todo:
+        _compile(*todo[0], extra_flags, verbose)
     return LIB
 
 

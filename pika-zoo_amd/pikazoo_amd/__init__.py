@@ -2,5 +2,19 @@
 
     from pikazoo_amd import pikazoo_v0
     env = pikazoo_v0.env(num_envs=65536, device="cuda:0", is_player2_computer=True)
+
+    from pikazoo_amd import learn                      # GAE over the trajectory tensors of a k-step launch, one launch
+    out = learn.gae(traj["rewards"], values, traj["terminations"])
 """
 from ._version import VERSION, __version__  # noqa: F401
+
+__all__ = ["VERSION", "__version__", "learn"]
+
+
+def __getattr__(name):
+    # `pikazoo_amd.learn` on first use: importing the package (and with it the step path) never loads that library
+    if name == "learn":
+        import importlib
+
+        return importlib.import_module(".learn", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

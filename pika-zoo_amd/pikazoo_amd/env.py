@@ -1142,6 +1142,22 @@ class raw_env(ParallelEnv):
             self._rew_raw[1].copy_(out["_rew"][1][-1])
             self._term_u8.copy_(out["_term"][-1])
 
+    def gae(self, traj: dict, values, gamma: float = 0.99, lam: float = 0.95, out: Optional[dict] = None):
+        """GAE(gamma, lam) advantages and returns of the trajectory a k-step launch returned (:meth:`rollout_random`,
+        :meth:`step_many` and their ``_held`` forms) in ONE launch: :func:`pikazoo_amd.learn.gae` on its ``rewards`` and
+        ``terminations``.  ``values``: ``{agent: [k + 1, N]}`` (float32, float16 or bfloat16; row k is the bootstrap) for
+        one or both agents, or one tensor for ``player_1``.  With ``frame_skip`` the rewards are per policy step, and so is
+        ``gamma``.  Returns ``{"advantages": ..., "returns": ...}`` in the shape of ``values``; pass it back as ``out``
+        to reuse its buffers."""
+        from . import learn  # (a library of its own: the step path never loads it)
+
+        rewards = traj["rewards"]
+        if isinstance(values, dict):
+            rewards = {agent: rewards[agent] for agent in values}
+        else:
+            rewards = rewards[self.possible_agents[0]]
+        return learn.gae(rewards, values, traj["terminations"], gamma, lam, out)
+
     def random_actions(self, action_seed: int, t: Optional[int] = None):
         """The policy stream of :meth:`step_random` as two ``int32[num_envs]`` device tensors."""
         if t is None:

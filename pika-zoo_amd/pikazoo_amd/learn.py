@@ -1,0 +1,180 @@
+"""What a trainer does first with the trajectory tensors of a k-step launch: GAE(gamma, lambda) in ONE launch.
+
+    from pikazoo_amd import learn
+    traj = env.rollout_random(action_seed, k=32)
+    out = learn.gae(traj["rewards"], values, traj["terminations"], gamma=0.99, lam=0.95)     # or env.gae(traj, values)
+    out["advantages"]["player_1"], out["returns"]["player_1"]                                # float32 [k, N]
+
+ctypes binding of libpikazoo_learn.so (C ABI and the exact arithmetic: include/pikazoo_learn.h), a library of its own
+beside the product library; nothing in the step path imports this module.  There is no torch fallback: a missing or
+stale library raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import torch
+
+from . import _native
+
+LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_learn.so"
+ABI_VERSION = 1
+REWARD_FORMATS = {torch.int32: 0, torch.float32: 1}
+VALUE_FORMATS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+_P = C.c_void_p
+SIGNATURES = {
+    "pz_learn_abi_version": (C.c_int, []),
+    "pz_learn_build_id": (C.c_char_p, []),
+    # (rew_p1, rew_p2, reward_format, terminated, val_p1, val_p2, value_format, k, n, the four pitches, gamma, lam,
+    #  adv_p1, adv_p2, ret_p1, ret_p2, stream)
+    "pz_gae": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                         C.c_int64, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+}
+_ERRORS = {-1: "a required pointer is NULL", -2: "a size, a pitch or a tensor too large for the kernel's addressing",
+           -3: "an unknown format, or gamma / lam outside [0, 1]", -4: "a pointer not aligned to its element"}
+_lib = None
+_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def load():
+    """Load libpikazoo_learn.so (once).  Raises, as ``_native.load()`` does, if it has not been built or was built from
+    other sources than the ones in this tree."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not LIB_PATH.exists():
+        raise _native.PikazooNativeError(
+            f"{LIB_PATH} is missing: build it with `python pika-zoo_amd/build.py` (hipcc --offload-arch=gfx950). "
+            "There is no torch fallback.")
+    if (_native.PKG_ROOT / "csrc" / "pz_learn.hip").exists():  # a source tree: the library must match it
+        b = _native._pz_build()
+        have, want = b.library_id(LIB_PATH), b.source_id()
+        if have != want:
+            raise _native.PikazooNativeError(
+                f"{LIB_PATH} is stale: built from sources {have}, the tree holds {want}; rebuild it with "
+                "`python pika-zoo_amd/build.py`")
+    lib = C.CDLL(str(LIB_PATH))
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the export is missing
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.pz_learn_abi_version() != ABI_VERSION:
+        raise _native.PikazooNativeError(f"ABI mismatch: library {lib.pz_learn_abi_version()} != binding {ABI_VERSION}")
+    _lib = lib
+    return lib
+
+
+def _sides(x, what):
+    """(keys or None, [tensor, ...]) of a tensor or an {agent: tensor} dict of one or two agents"""
+    if isinstance(x, dict):
+        if not 1 <= len(x) <= 2:
+            raise ValueError(f"{what}: a dict of one or two agents, got {len(x)}")
+        keys, vals = list(x), list(x.values())
+    else:
+        keys, vals = None, [x]
+    for v in vals:
+        if not isinstance(v, torch.Tensor):
+            raise ValueError(f"{what} must be a tensor or a dict of tensors, got {type(v).__name__}")
+    return keys, vals
+
+
+def _pitch(ts, rows, n, what):
+    """the row pitch, in elements, that the tensors of `ts` ([rows, n], last dimension contiguous) share"""
+    pitches = set()
+    for t in ts:
+        if n > 1 and t.stride(1) != 1:
+            raise ValueError(f"{what}: the last dimension must be contiguous (stride {t.stride(1)})")
+        pitches.add(max(int(t.stride(0)), n) if rows > 1 else n)
+        if rows > 1 and t.stride(0) < n:
+            raise ValueError(f"{what}: rows overlap (row stride {t.stride(0)} < {n})")
+    if len(pitches) != 1:
+        raise ValueError(f"{what}: both agents' tensors must have the same row stride, got {sorted(pitches)}")
+    return pitches.pop()
+
+
+def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, out: Optional[dict] = None):
+    """GAE(gamma, lam) advantages and returns of one or both agents in one launch (``pz_gae``).
+
+    ``rewards``: ``[k, N]`` int32 or float32, ``values``: ``[k + 1, N]`` float32, float16 or bfloat16 (row t is the value
+    of the observation the action of step t was chosen on, row k the bootstrap) -- tensors, or ``{agent: tensor}`` dicts
+    with the same one or two agents; ``terminations``: ``[k, N]`` bool or uint8, shared by the agents (a dict: every
+    entry must be that one tensor's).  The last dimension is contiguous, any row stride >= N goes.  Returns
+    ``{"advantages": ..., "returns": ...}``, float32 ``[k, N]``, in the shape of ``rewards`` (dicts for dicts).
+
+    The arithmetic is pinned (include/pikazoo_learn.h): float32, round to nearest even, no fused multiply-add, nothing
+    crosses an episode end.  The launch goes to the caller's current stream without a synchronisation, and without an
+    allocation when ``out`` is the previous result of the same shapes: it can be captured into a graph.  Shape, dtype,
+    device and range errors raise ``ValueError`` before any launch.  The outputs must not alias the inputs."""
+    keys, rew = _sides(rewards, "rewards")
+    vkeys, val = _sides(values, "values")
+    if vkeys != keys:
+        raise ValueError(f"rewards and values must name the same agents in the same order: {keys} and {vkeys}")
+    if isinstance(terminations, dict):
+        flags = list(terminations.values())
+        if not flags or any(not isinstance(f, torch.Tensor) for f in flags) or any(
+                f.data_ptr() != flags[0].data_ptr() or f.shape != flags[0].shape or f.stride() != flags[0].stride()
+                for f in flags[1:]):
+            raise ValueError("terminations: the agents share one tensor of flags")
+        term = flags[0]
+    else:
+        term = terminations
+    if not isinstance(term, torch.Tensor):
+        raise ValueError(f"terminations must be a tensor, got {type(term).__name__}")
+    r0 = rew[0]
+    if r0.dim() != 2 or r0.shape[0] < 1:
+        raise ValueError(f"rewards must have shape [k, N] with k >= 1, got {tuple(r0.shape)}")
+    k, n = int(r0.shape[0]), int(r0.shape[1])
+    dev = r0.device
+    if dev.type != "cuda":
+        raise ValueError(f"gae() runs on the GPU: rewards are on {dev}")
+    for name, ts, shape, dtypes in (("rewards", rew, (k, n), (r0.dtype,) if r0.dtype in REWARD_FORMATS else tuple(REWARD_FORMATS)),
+                                    ("values", val, (k + 1, n), (val[0].dtype,) if val[0].dtype in VALUE_FORMATS else tuple(VALUE_FORMATS)),
+                                    ("terminations", [term], (k, n), (torch.bool, torch.uint8))):
+        for t in ts:
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"{name} are on {t.device}, rewards on {dev}")
+    gamma, lam = float(gamma), float(lam)
+    for name, x in (("gamma", gamma), ("lam", lam)):
+        if not (math.isfinite(x) and 0.0 <= x <= 1.0):
+            raise ValueError(f"{name} must lie in [0, 1], got {x}")
+    rew_pitch, val_pitch = _pitch(rew, k, n, "rewards"), _pitch(val, k + 1, n, "values")
+    term_pitch = _pitch([term], k, n, "terminations")
+
+    adv = ret = None
+    if out is not None:
+        a, r = out.get("advantages"), out.get("returns")
+        akeys, adv = _sides(a, "out['advantages']")
+        rkeys, ret = _sides(r, "out['returns']")
+        if akeys != keys or rkeys != keys:
+            raise ValueError(f"out= holds the agents {akeys} / {rkeys}, the call {keys}")
+        for t in adv + ret:
+            if tuple(t.shape) != (k, n) or t.dtype != torch.float32 or t.device != dev:
+                raise ValueError(f"out= must hold float32 [{k}, {n}] tensors on {dev}")
+        out_pitch = _pitch(adv + ret, k, n, "out=")
+    else:
+        adv = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
+        ret = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
+        out_pitch = n
+        out = {"advantages": dict(zip(keys, adv)) if keys is not None else adv[0],
+               "returns": dict(zip(keys, ret)) if keys is not None else ret[0]}
+    if n == 0:
+        return out
+    lib = load()
+    two = len(rew) == 2
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(index):
+        stream = _get_raw_stream(index) if _get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
+        code = lib.pz_gae(rew[0].data_ptr(), rew[1].data_ptr() if two else None, REWARD_FORMATS[r0.dtype], term.data_ptr(),
+                          val[0].data_ptr(), val[1].data_ptr() if two else None, VALUE_FORMATS[val[0].dtype], k, n,
+                          rew_pitch, term_pitch, val_pitch, out_pitch, gamma, lam, adv[0].data_ptr(),
+                          adv[1].data_ptr() if two else None, ret[0].data_ptr(), ret[1].data_ptr() if two else None, stream)
+    if code != 0:
+        raise _native.PikazooNativeError(f"pz_gae failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+    return out
