@@ -71,6 +71,13 @@ def main():
     print("gae: advantages", tuple(targets["advantages"]["player_1"].shape), targets["advantages"]["player_1"].dtype,
           "| returns", tuple(targets["returns"]["player_2"].shape))
 
+    # what it does on every policy step: sample from the policy net's logits -- action, log-prob and entropy of both agents
+    # in ONE launch (pikazoo_amd.policy, a library of its own; env seed, game ids and step counter feed its Philox stream)
+    logits = {agent: torch.randn(n, env.action_space(agent).n, device="cuda:0") for agent in env.agents}
+    picked = raw.sample_actions(logits)
+    env.step(picked["actions"])  # int64, read as they are
+    print("sample_actions:", picked["actions"]["player_1"].dtype, "| mean entropy %.3f" % float(picked["entropy"]["player_1"].mean()))
+
     # a larger batch in the packed state format (36 instead of 176 bytes of state per game; same results) and with int16
     # observations (same values, half the bytes): this is where the step launch streams HBM, and fewer bytes are less time
     for fmt, odt in (("int32", torch.int32), ("packed", torch.int32), ("packed", torch.int16)):

@@ -1,0 +1,518 @@
+// libpikazoo_policy.so (include/pikazoo_policy.h): the categorical policy head over [n, A] logits -- sample + log-prob +
+// entropy in one launch, log-prob + entropy of given actions, and the backward of that pair.
+//
+// One lane owns one game's row and does the serial work over it; blockIdx.y = agent; one wave (64 consecutive games) per
+// workgroup.  A wave's 64 rows are one contiguous span of (rows - 1) * pitch + A elements, and 64 lanes each walking a
+// 72-byte row would be 64 strided segments per load instruction.  So the span is read in 16-byte pieces, lane after lane
+// (stage_span), and transposed through LDS: every element lands as a float32 at [row * stride + column] of the wave's
+// image, where its lane then finds its row.  The image's row stride is A | 1 dwords: an odd stride puts the 32 lanes of a
+// ds_read_b32 group on 32 different banks (A = 18 as it stands would put lanes l and l + 16 on one bank, 2-way).
+//   * A span that starts or ends off 16-byte alignment (an odd pitch in a 2-byte format, a base pointer one element into
+//     a buffer) keeps the wide loads for its aligned middle: only the elements in front of the first and behind the last
+//     whole 16-byte piece are loaded one by one, by one lane each.  Nothing outside the span is read.
+//   * The wide loads are issued a group at a time with no condition around any of them (a lane whose piece lies behind
+//     the span re-reads the last whole piece and drops it), so that they are all in flight together.
+//   * A pitch above kMaxStagedPitch (a view into a much wider tensor) would mostly load pad columns: there the A live
+//     columns are gathered element by element, 64 consecutive (row, column) pairs per instruction.
+// The passes over the row re-read the image (A is a runtime value: a register array indexed by it would live in scratch).
+// The backward writes its row into the same image and the wave stores it transposed back: whole 16-byte pieces where the
+// gradient rows are dense (grad_pitch == A), element by element where pad columns, which are not written, lie between.
+//
+// The logit format is a compile-time instantiation (3 formats x 3 launches = 9 kernels); A, the pitches and the action
+// format are runtime values.  Contraction may stay on -- nothing here is pinned against a host restatement -- but the one
+// product-sum whose bits two kernels must share (the entropy's) is an explicit fmaf, and the row statistics of all three
+// kernels are the same function.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "pikazoo_hip.h"
+#include "pikazoo_policy.h"
+
+namespace pz_policy {
+
+constexpr int kLanes = 64;            // games per workgroup: one wave
+constexpr int kMaxActions = 32;
+constexpr int kMaxStride = kMaxActions | 1;  // dwords per row of the LDS image, at most
+constexpr int kMaxStagedPitch = 64;   // above it the live columns are gathered instead of the span staged
+constexpr int kDivShift = 20;         // idx / d == (idx * ceil(2^20 / d)) >> 20 for idx < 64 * 64 + 8, 2 <= d <= 64
+
+struct Common {
+    const void* logits[2];
+    const void* act[2];  // (written by the sample launch)
+    float* logp[2];
+    float* ent[2];
+    int64_t n, pitch;
+    int32_t A, action_format;
+    uint32_t pitch_magic, a_magic;  // ceil(2^20 / pitch) (0 when the pitch is gathered), ceil(2^20 / A)
+};
+
+struct SampleArgs {
+    Common c;
+    const uint64_t* step_dev;
+    uint64_t step;
+    int64_t first_game;
+    uint32_t key0, key1;
+};
+
+struct BackwardArgs {
+    Common c;
+    const float* glogp[2];
+    const float* gent[2];
+    void* grad[2];
+    int64_t grad_pitch;
+};
+
+template <int LF>
+struct Raw {
+    using type = uint16_t;
+};
+template <>
+struct Raw<PZ_POLICY_LOGIT_FLOAT32> {
+    using type = uint32_t;
+};
+
+template <int LF>
+__device__ __forceinline__ float to_float(typename Raw<LF>::type bits)
+{
+    if constexpr (LF == PZ_POLICY_LOGIT_FLOAT32)
+        return __uint_as_float(bits);
+    else if constexpr (LF == PZ_POLICY_LOGIT_FLOAT16)
+        return (float)__builtin_bit_cast(_Float16, bits);  // exact
+    else
+        return __uint_as_float((uint32_t)bits << 16);  // bfloat16 is the upper half of a float32: exact
+}
+
+// round to nearest even into the logits' own format
+template <int LF>
+__device__ __forceinline__ typename Raw<LF>::type from_float(float x)
+{
+    if constexpr (LF == PZ_POLICY_LOGIT_FLOAT32) {
+        return __float_as_uint(x);
+    } else if constexpr (LF == PZ_POLICY_LOGIT_FLOAT16) {
+        return __builtin_bit_cast(uint16_t, (_Float16)x);
+    } else {
+        const uint32_t b = __float_as_uint(x);
+        if (x != x) return (uint16_t)((b >> 16) | 0x40u);  // a NaN stays one
+        return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+    }
+}
+
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+// element j of a 16-byte piece
+template <int LF>
+__device__ __forceinline__ typename Raw<LF>::type piece_element(const u32x4& v, int j)
+{
+    if constexpr (LF == PZ_POLICY_LOGIT_FLOAT32)
+        return v[j];
+    else
+        return (uint16_t)(v[j >> 1] >> (16 * (j & 1)));
+}
+
+// ---- global -> LDS: the wave's span, transposed -------------------------------------------------------------------------
+// `span`: the first element of the wave's first row; `len` = (rows - 1) * pitch + A elements.  image[row * stride + col]
+// receives every element with col < A as a float32.
+template <int LF>
+__device__ __forceinline__ void stage_span(const typename Raw<LF>::type* span, int len, int pitch, uint32_t magic, int A, int stride,
+                                           float* image, int lane)
+{
+    using R = typename Raw<LF>::type;
+    constexpr int E = 16 / (int)sizeof(R);       // elements per piece
+    constexpr int kGroup = sizeof(R) == 4 ? 5 : 3;  // pieces per lane in flight: one group covers 64 rows at pitch 19 (20)
+    const int mis = (int)(((uintptr_t)span & 15) / sizeof(R));   // elements between the 16-byte boundary below and `span`
+    const int head = mis ? min(E - mis, len) : 0;               // elements in front of the first whole piece
+    const int pieces = (len - head) / E;                         // whole pieces
+    const int tail = len - head - pieces * E;                    // elements behind the last whole piece
+    auto put = [&](int idx, R bits) {
+        const int row = (int)(((uint32_t)idx * magic) >> kDivShift), col = idx - row * pitch;
+        if (col < A) image[row * stride + col] = to_float<LF>(bits);
+    };
+    // the peeled ends: lanes 0 .. head-1 and 32 .. 32+tail-1, one element each (head, tail < E <= 8)
+    if (lane < head) put(lane, span[lane]);
+    if (lane >= 32 && lane - 32 < tail) put(head + pieces * E + lane - 32, span[head + pieces * E + lane - 32]);
+    const u32x4* body = (const u32x4*)(span + head);  // 16-byte aligned
+    for (int p0 = 0; p0 < pieces; p0 += kGroup * kLanes) {
+        u32x4 v[kGroup];
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) v[k] = body[min(p0 + k * kLanes + lane, pieces - 1)];
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) {
+            const int p = p0 + k * kLanes + lane;
+            if (p < pieces) {
+#pragma unroll
+                for (int j = 0; j < E; ++j) put(head + p * E + j, piece_element<LF>(v[k], j));
+            }
+        }
+    }
+}
+
+// the same image from a wide pitch: 64 consecutive (row, column < A) pairs per load instruction
+template <int LF>
+__device__ __forceinline__ void gather_rows(const typename Raw<LF>::type* span, int rows, int64_t pitch, uint32_t a_magic, int A,
+                                            int stride, float* image, int lane)
+{
+    const int count = rows * A;
+#pragma unroll 4
+    for (int e = lane; e < count; e += kLanes) {
+        const int row = (int)(((uint32_t)e * a_magic) >> kDivShift), col = e - row * A;
+        image[row * stride + col] = to_float<LF>(span[row * pitch + col]);
+    }
+}
+
+template <int LF>
+__device__ __forceinline__ void load_image(const Common& c, int side, int64_t g0, int rows, int stride, float* image, int lane)
+{
+    using R = typename Raw<LF>::type;
+    const R* span = (const R*)c.logits[side] + g0 * c.pitch;
+    if (c.pitch <= kMaxStagedPitch)
+        stage_span<LF>(span, (rows - 1) * (int)c.pitch + c.A, (int)c.pitch, c.pitch_magic, c.A, stride, image, lane);
+    else
+        gather_rows<LF>(span, rows, c.pitch, c.a_magic, c.A, stride, image, lane);
+    __syncthreads();  // (one wave: no s_barrier, the LDS writes are waited for)
+}
+
+// ---- the row ------------------------------------------------------------------------------------------------------------
+struct RowStats {
+    float m, S, logS, H;
+    int last;  // the last index with e_i > 0
+    bool bad;  // step 6 of the header: a NaN, a +inf, or no finite logit
+};
+
+// steps 1, 2 and the entropy of step 5; every kernel runs exactly this text
+__device__ __forceinline__ RowStats row_stats(const float* row, int A)
+{
+    RowStats s;
+    float m = -INFINITY;
+    bool bad = false;
+    for (int i = 0; i < A; ++i) {
+        const float l = row[i];
+        bad |= !(l < INFINITY);  // NaN or +inf
+        m = fmaxf(m, l);
+    }
+    bad |= m == -INFINITY;
+    float c = 0.0f, t = 0.0f;
+    int last = 0;
+    for (int i = 0; i < A; ++i) {
+        const float d = row[i] - m;
+        const float e = expf(d);
+        c += e;
+        if (e > 0.0f) {
+            t = fmaf(e, d, t);
+            last = i;
+        }
+    }
+    s.m = m, s.S = c, s.logS = logf(c), s.last = last, s.bad = bad;
+    s.H = s.logS - t / c;
+    return s;
+}
+
+__device__ __forceinline__ int load_action(const void* act, int format, int64_t g)
+{
+    if (format == PZ_POLICY_ACTION_INT32) return ((const int32_t*)act)[g];
+    const int64_t a = ((const int64_t*)act)[g];
+    return a == (int32_t)a ? (int32_t)a : -1;  // (beyond int32: out of range either way)
+}
+
+// step 5's log-prob, and the stores of one game
+__device__ __forceinline__ void finish(const Common& c, int side, int64_t g, const float* row, const RowStats& s, int a)
+{
+    const bool in_range = (unsigned)a < (unsigned)c.A;
+    const float la = row[in_range ? a : 0];
+    const float nan = __uint_as_float(0x7FC00000u);
+    const float logp = (la - s.m) - s.logS;
+    if (c.logp[side]) c.logp[side][g] = (s.bad || !in_range) ? nan : logp;
+    if (c.ent[side]) c.ent[side][g] = s.bad ? nan : s.H;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& o0,
+                                              uint32_t& o1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        c0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        c1 = (uint32_t)p1;
+        c2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o0 = c0;
+    o1 = c1;
+}
+
+template <int LF>
+__global__ void __launch_bounds__(kLanes) sample_kernel(const SampleArgs a)
+{
+    __shared__ float image[kLanes * kMaxStride];
+    const Common& c = a.c;
+    const int lane = threadIdx.x, side = blockIdx.y;
+    const int64_t g0 = (int64_t)blockIdx.x * kLanes;
+    const int rows = (int)min((int64_t)kLanes, c.n - g0);
+    const int stride = c.A | 1;
+    load_image<LF>(c, side, g0, rows, stride, image, lane);
+    if (lane >= rows) return;
+    const int64_t g = g0 + lane;
+    const float* row = image + lane * stride;
+    const RowStats s = row_stats(row, c.A);
+    // step 3: the draw
+    const uint64_t T = a.step + (a.step_dev ? *a.step_dev : 0);
+    const uint64_t G = (uint64_t)(a.first_game + g);
+    uint32_t w0, w1;
+    philox4x32_10((uint32_t)G, (uint32_t)(G >> 32), (uint32_t)T, 2u + 4u * (uint32_t)(T >> 32), a.key0, a.key1, w0, w1);
+    const float u = (float)((side ? w1 : w0) >> 8) * 0x1p-24f;
+    // step 4: the same sums again (the same expf of the same arguments: the same c_i), counted against the threshold
+    const float thr = u * s.S;
+    float cum = 0.0f;
+    int act = 0;
+    for (int i = 0; i < c.A - 1; ++i) {
+        cum += expf(row[i] - s.m);
+        act += cum <= thr;
+    }
+    act = s.bad ? 0 : min(act, s.last);
+    if (c.action_format == PZ_POLICY_ACTION_INT32)
+        ((int32_t*)c.act[side])[g] = act;
+    else
+        ((int64_t*)c.act[side])[g] = act;
+    finish(c, side, g, row, s, act);
+}
+
+template <int LF>
+__global__ void __launch_bounds__(kLanes) log_probs_kernel(const Common c)
+{
+    __shared__ float image[kLanes * kMaxStride];
+    const int lane = threadIdx.x, side = blockIdx.y;
+    const int64_t g0 = (int64_t)blockIdx.x * kLanes;
+    const int rows = (int)min((int64_t)kLanes, c.n - g0);
+    const int stride = c.A | 1;
+    load_image<LF>(c, side, g0, rows, stride, image, lane);
+    if (lane >= rows) return;
+    const int64_t g = g0 + lane;
+    const float* row = image + lane * stride;
+    const RowStats s = row_stats(row, c.A);
+    finish(c, side, g, row, s, load_action(c.act[side], c.action_format, g));
+}
+
+// ---- LDS -> global: the gradient rows, transposed back --------------------------------------------------------------------
+// dense rows (grad_pitch == A): the span of rows * A elements in 16-byte pieces, the ends peeled as in stage_span
+template <int LF>
+__device__ __forceinline__ void store_dense(typename Raw<LF>::type* span, int len, int A, uint32_t magic, int stride, const float* image,
+                                            int lane)
+{
+    using R = typename Raw<LF>::type;
+    constexpr int E = 16 / (int)sizeof(R);
+    const int mis = (int)(((uintptr_t)span & 15) / sizeof(R));
+    const int head = mis ? min(E - mis, len) : 0;
+    const int pieces = (len - head) / E;
+    const int tail = len - head - pieces * E;
+    auto get = [&](int idx) {
+        const int row = (int)(((uint32_t)idx * magic) >> kDivShift), col = idx - row * A;
+        return from_float<LF>(image[row * stride + col]);
+    };
+    if (lane < head) span[lane] = get(lane);
+    if (lane >= 32 && lane - 32 < tail) span[head + pieces * E + lane - 32] = get(head + pieces * E + lane - 32);
+    u32x4* body = (u32x4*)(span + head);
+    for (int p = lane; p < pieces; p += kLanes) {
+        u32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (sizeof(R) == 4)
+                v[j] = get(head + p * E + j);
+            else
+                v[j] = (uint32_t)get(head + p * E + 2 * j) | ((uint32_t)get(head + p * E + 2 * j + 1) << 16);
+        }
+        body[p] = v;
+    }
+}
+
+template <int LF>
+__global__ void __launch_bounds__(kLanes) backward_kernel(const BackwardArgs a)
+{
+    __shared__ float image[kLanes * kMaxStride];
+    using R = typename Raw<LF>::type;
+    const Common& c = a.c;
+    const int lane = threadIdx.x, side = blockIdx.y;
+    const int64_t g0 = (int64_t)blockIdx.x * kLanes;
+    const int rows = (int)min((int64_t)kLanes, c.n - g0);
+    const int A = c.A, stride = A | 1;
+    load_image<LF>(c, side, g0, rows, stride, image, lane);
+    if (lane < rows) {
+        const int64_t g = g0 + lane;
+        float* row = image + lane * stride;
+        const RowStats s = row_stats(row, A);
+        const int act = load_action(c.act[side], c.action_format, g);
+        const float glogp = a.glogp[side] ? a.glogp[side][g] : 0.0f;
+        const float gent = a.gent[side] ? a.gent[side][g] : 0.0f;
+        const float nan = __uint_as_float(0x7FC00000u);
+        for (int i = 0; i < A; ++i) {
+            const float d = row[i] - s.m;
+            const float e = expf(d);
+            const float p = e / s.S;
+            float grad = glogp * ((i == act ? 1.0f : 0.0f) - p);
+            if (e > 0.0f) grad += gent * (-p * ((d - s.logS) + s.H));
+            row[i] = s.bad ? nan : grad;
+        }
+    }
+    __syncthreads();
+    R* span = (R*)a.grad[side] + g0 * a.grad_pitch;
+    if (a.grad_pitch == A) {
+        store_dense<LF>(span, rows * A, A, c.a_magic, stride, image, lane);
+    } else {
+        const int count = rows * A;
+        for (int e = lane; e < count; e += kLanes) {
+            const int row = (int)(((uint32_t)e * c.a_magic) >> kDivShift), col = e - row * A;
+            span[row * a.grad_pitch + col] = from_float<LF>(image[row * stride + col]);
+        }
+    }
+}
+
+static dim3 grid_of(int64_t n, bool both) { return dim3((unsigned)((n + kLanes - 1) / kLanes), both ? 2 : 1); }
+
+static uint32_t magic_of(int64_t d) { return (uint32_t)((((int64_t)1 << kDivShift) + d - 1) / d); }
+
+static bool misaligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) != 0; }
+
+static bool known_logit_format(int f)
+{
+    return f == PZ_POLICY_LOGIT_FLOAT32 || f == PZ_POLICY_LOGIT_FLOAT16 || f == PZ_POLICY_LOGIT_BFLOAT16;
+}
+
+static bool known_action_format(int f) { return f == PZ_POLICY_ACTION_INT32 || f == PZ_POLICY_ACTION_INT64; }
+
+// agent 2's pointer is there exactly where agent 1's is, if agent 2 is there at all
+static bool paired(const void* p1, const void* p2, bool both) { return (p2 != nullptr) == (both && p1 != nullptr); }
+
+static bool bad_sizes(int32_t A, int64_t n, int64_t pitch)
+{
+    if (n < 0 || n > ((int64_t)1 << 30)) return true;
+    if (A < 2 || A > kMaxActions || pitch < A) return true;
+    return n > 0 && pitch > (INT64_MAX / 4) / n;  // n * pitch * 4 bytes: refused, never wrapped
+}
+
+static Common common_of(const void* l1, const void* l2, int32_t A, int64_t n, int64_t pitch, int32_t action_format, const void* a1,
+                        const void* a2, float* lp1, float* lp2, float* e1, float* e2)
+{
+    return Common{{l1, l2}, {a1, a2}, {lp1, lp2}, {e1, e2}, n, pitch, A, action_format, pitch <= kMaxStagedPitch ? magic_of(pitch) : 0u,
+                  magic_of(A)};
+}
+
+}  // namespace pz_policy
+
+using namespace pz_policy;
+
+extern "C" {
+
+#ifndef PZ_BUILD_ID
+#define PZ_BUILD_ID "unknown"
+#endif
+// (the same record the product library carries: build.py reads it from the file's bytes)
+static const char kPolicyBuildIdRecord[] = "pz_build_id:" PZ_BUILD_ID;
+const char* pz_policy_build_id(void) { return kPolicyBuildIdRecord + 12; }
+
+int pz_policy_abi_version(void) { return PZ_POLICY_ABI_VERSION; }
+
+int pz_sample_actions(const void* logits_p1, const void* logits_p2, int32_t logit_format, int32_t num_actions, int64_t n,
+                      int64_t logit_pitch, uint64_t seed, int64_t first_game, uint64_t step, const uint64_t* step_dev,
+                      int32_t action_format, void* act_p1, void* act_p2, float* logp_p1, float* logp_p2, float* ent_p1, float* ent_p2,
+                      void* stream)
+{
+    if (!logits_p1 || !act_p1) return PZ_E_NULL;
+    const bool both = logits_p2 != nullptr;
+    if (!paired(act_p1, act_p2, both) || !paired(logp_p1, logp_p2, both) || !paired(ent_p1, ent_p2, both)) return PZ_E_NULL;
+    if (bad_sizes(num_actions, n, logit_pitch)) return PZ_E_SIZE;
+    if (first_game < 0 || step >= ((uint64_t)1 << 62)) return PZ_E_SIZE;
+    if (!known_logit_format(logit_format) || !known_action_format(action_format)) return PZ_E_CONFIG;
+    const uintptr_t lb = logit_format == PZ_POLICY_LOGIT_FLOAT32 ? 4 : 2, ab = action_format == PZ_POLICY_ACTION_INT32 ? 4 : 8;
+    if (misaligned(logits_p1, lb) || misaligned(logits_p2, lb) || misaligned(act_p1, ab) || misaligned(act_p2, ab) ||
+        misaligned(logp_p1, 4) || misaligned(logp_p2, 4) || misaligned(ent_p1, 4) || misaligned(ent_p2, 4) || misaligned(step_dev, 8))
+        return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    const SampleArgs a{common_of(logits_p1, logits_p2, num_actions, n, logit_pitch, action_format, act_p1, act_p2, logp_p1, logp_p2,
+                                 ent_p1, ent_p2),
+                       step_dev, step, first_game, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    const dim3 grid = grid_of(n, both);
+    switch (logit_format) {
+        case PZ_POLICY_LOGIT_FLOAT32:
+            hipLaunchKernelGGL((sample_kernel<PZ_POLICY_LOGIT_FLOAT32>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+        case PZ_POLICY_LOGIT_FLOAT16:
+            hipLaunchKernelGGL((sample_kernel<PZ_POLICY_LOGIT_FLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+        default:
+            hipLaunchKernelGGL((sample_kernel<PZ_POLICY_LOGIT_BFLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+    }
+    return (int)hipGetLastError();
+}
+
+int pz_action_log_probs(const void* logits_p1, const void* logits_p2, int32_t logit_format, int32_t num_actions, int64_t n,
+                        int64_t logit_pitch, int32_t action_format, const void* act_p1, const void* act_p2, float* logp_p1,
+                        float* logp_p2, float* ent_p1, float* ent_p2, void* stream)
+{
+    if (!logits_p1 || !act_p1) return PZ_E_NULL;
+    const bool both = logits_p2 != nullptr;
+    if (!paired(act_p1, act_p2, both) || !paired(logp_p1, logp_p2, both) || !paired(ent_p1, ent_p2, both)) return PZ_E_NULL;
+    if (bad_sizes(num_actions, n, logit_pitch)) return PZ_E_SIZE;
+    if (!known_logit_format(logit_format) || !known_action_format(action_format)) return PZ_E_CONFIG;
+    const uintptr_t lb = logit_format == PZ_POLICY_LOGIT_FLOAT32 ? 4 : 2, ab = action_format == PZ_POLICY_ACTION_INT32 ? 4 : 8;
+    if (misaligned(logits_p1, lb) || misaligned(logits_p2, lb) || misaligned(act_p1, ab) || misaligned(act_p2, ab) ||
+        misaligned(logp_p1, 4) || misaligned(logp_p2, 4) || misaligned(ent_p1, 4) || misaligned(ent_p2, 4))
+        return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    const Common c = common_of(logits_p1, logits_p2, num_actions, n, logit_pitch, action_format, act_p1, act_p2, logp_p1, logp_p2,
+                               ent_p1, ent_p2);
+    const dim3 grid = grid_of(n, both);
+    switch (logit_format) {
+        case PZ_POLICY_LOGIT_FLOAT32:
+            hipLaunchKernelGGL((log_probs_kernel<PZ_POLICY_LOGIT_FLOAT32>), grid, dim3(kLanes), 0, (hipStream_t)stream, c);
+            break;
+        case PZ_POLICY_LOGIT_FLOAT16:
+            hipLaunchKernelGGL((log_probs_kernel<PZ_POLICY_LOGIT_FLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, c);
+            break;
+        default:
+            hipLaunchKernelGGL((log_probs_kernel<PZ_POLICY_LOGIT_BFLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, c);
+            break;
+    }
+    return (int)hipGetLastError();
+}
+
+int pz_action_log_probs_backward(const void* logits_p1, const void* logits_p2, int32_t logit_format, int32_t num_actions, int64_t n,
+                                 int64_t logit_pitch, int32_t action_format, const void* act_p1, const void* act_p2,
+                                 const float* glogp_p1, const float* glogp_p2, const float* gent_p1, const float* gent_p2, void* grad_p1,
+                                 void* grad_p2, int64_t grad_pitch, void* stream)
+{
+    if (!logits_p1 || !act_p1 || !grad_p1 || (!glogp_p1 && !gent_p1)) return PZ_E_NULL;
+    const bool both = logits_p2 != nullptr;
+    if (!paired(act_p1, act_p2, both) || !paired(glogp_p1, glogp_p2, both) || !paired(gent_p1, gent_p2, both) ||
+        !paired(grad_p1, grad_p2, both))
+        return PZ_E_NULL;
+    if (bad_sizes(num_actions, n, logit_pitch) || bad_sizes(num_actions, n, grad_pitch)) return PZ_E_SIZE;
+    if (!known_logit_format(logit_format) || !known_action_format(action_format)) return PZ_E_CONFIG;
+    const uintptr_t lb = logit_format == PZ_POLICY_LOGIT_FLOAT32 ? 4 : 2, ab = action_format == PZ_POLICY_ACTION_INT32 ? 4 : 8;
+    if (misaligned(logits_p1, lb) || misaligned(logits_p2, lb) || misaligned(act_p1, ab) || misaligned(act_p2, ab) ||
+        misaligned(glogp_p1, 4) || misaligned(glogp_p2, 4) || misaligned(gent_p1, 4) || misaligned(gent_p2, 4) ||
+        misaligned(grad_p1, lb) || misaligned(grad_p2, lb))
+        return PZ_E_ALIGN;
+    if (n == 0) return PZ_OK;
+    const BackwardArgs a{common_of(logits_p1, logits_p2, num_actions, n, logit_pitch, action_format, act_p1, act_p2, nullptr, nullptr,
+                                   nullptr, nullptr),
+                         {glogp_p1, glogp_p2}, {gent_p1, gent_p2}, {grad_p1, grad_p2}, grad_pitch};
+    const dim3 grid = grid_of(n, both);
+    switch (logit_format) {
+        case PZ_POLICY_LOGIT_FLOAT32:
+            hipLaunchKernelGGL((backward_kernel<PZ_POLICY_LOGIT_FLOAT32>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+        case PZ_POLICY_LOGIT_FLOAT16:
+            hipLaunchKernelGGL((backward_kernel<PZ_POLICY_LOGIT_FLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+        default:
+            hipLaunchKernelGGL((backward_kernel<PZ_POLICY_LOGIT_BFLOAT16>), grid, dim3(kLanes), 0, (hipStream_t)stream, a);
+            break;
+    }
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -5,16 +5,20 @@
 
     from pikazoo_amd import learn                      # GAE over the trajectory tensors of a k-step launch, one launch
     out = learn.gae(traj["rewards"], values, traj["terminations"])
+
+    from pikazoo_amd import policy                     # the categorical head: sample + log-prob + entropy, one launch
+    out = policy.sample(logits, seed=7, step=env.steps_done)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn"]
+__all__ = ["VERSION", "__version__", "learn", "policy"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` on first use: importing the package (and with it the step path) never loads that library
-    if name == "learn":
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` on first use: importing the package (and with it the step path) never
+    # loads those libraries
+    if name in ("learn", "policy"):
         import importlib
 
-        return importlib.import_module(".learn", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

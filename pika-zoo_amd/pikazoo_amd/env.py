@@ -1158,6 +1158,22 @@ class raw_env(ParallelEnv):
             rewards = rewards[self.possible_agents[0]]
         return learn.gae(rewards, values, traj["terminations"], gamma, lam, out)
 
+    def sample_actions(self, logits, step=None, out: Optional[dict] = None):
+        """Sample this env's actions from policy logits in ONE launch: :func:`pikazoo_amd.policy.sample` with
+        ``seed=self.seed``, ``first_game=self.env_id_base`` and ``step=self.steps_done`` (or ``step``: an int, or a
+        1-element int64 device tensor for a captured graph).  ``logits``: ``{agent: [num_envs, A]}`` for one or both
+        agents, or one tensor, with ``A == n_actions`` (13 under a fused ``SimplifyAction``).  The draws share nothing
+        with the env's own random stream although they share its seed.  Returns ``{"actions", "log_probs",
+        "entropy"}``; its ``"actions"`` go into :meth:`step` as they are.  Pass it back as ``out`` to reuse its buffers."""
+        from . import policy  # (a library of its own: the step path never loads it)
+
+        for t in (logits.values() if isinstance(logits, dict) else [logits]):
+            if isinstance(t, torch.Tensor) and (t.dim() != 2 or t.shape[0] != self.num_envs or t.shape[1] != self.n_actions):
+                raise ValueError(f"logits must have shape [{self.num_envs}, {self.n_actions}] (this env's games and actions), "
+                                 f"got {list(t.shape)}")
+        return policy.sample(logits, self.seed & 0xFFFFFFFFFFFFFFFF, self.steps_done if step is None else step, self.env_id_base,
+                             out=out)
+
     def random_actions(self, action_seed: int, t: Optional[int] = None):
         """The policy stream of :meth:`step_random` as two ``int32[num_envs]`` device tensors."""
         if t is None:
