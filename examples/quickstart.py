@@ -78,6 +78,20 @@ def main():
     env.step(picked["actions"])  # int64, read as they are
     print("sample_actions:", picked["actions"]["player_1"].dtype, "| mean entropy %.3f" % float(picked["entropy"]["player_1"].mean()))
 
+    # and what closes the loop on every minibatch: the clipped PPO loss, its logging statistics and BOTH gradients from one
+    # pass over the logit rows (pikazoo_amd.ppo, a library of its own).  `head` stands for the policy net's [n, A + 1] output,
+    # logits and value from one Linear; a trainer flattens the targets and indexes them by the minibatch (here: step 0)
+    from pikazoo_amd import ppo
+
+    A = env.action_space("player_1").n
+    head = {agent: torch.randn(n, A + 1, device="cuda:0", requires_grad=True) for agent in env.agents}
+    loss, stats = ppo.loss(head=head, num_actions=A, actions=picked["actions"], old_log_probs=picked["log_probs"],
+                           advantages={a: targets["advantages"][a][0] for a in env.agents},
+                           returns={a: targets["returns"][a][0] for a in env.agents})
+    (loss["player_1"] + loss["player_2"]).backward()
+    print("ppo.loss: %.4f" % float(stats["loss"]["player_1"]), "| approx_kl %.4f" % float(stats["approx_kl"]["player_1"]),
+          "| clip_fraction %.3f" % float(stats["clip_fraction"]["player_1"]), "| grad", tuple(head["player_1"].grad.shape))
+
     # a larger batch in the packed state format (36 instead of 176 bytes of state per game; same results) and with int16
     # observations (same values, half the bytes): this is where the step launch streams HBM, and fewer bytes are less time
     for fmt, odt in (("int32", torch.int32), ("packed", torch.int32), ("packed", torch.int16)):

@@ -8,16 +8,19 @@
 
     from pikazoo_amd import policy                     # the categorical head: sample + log-prob + entropy, one launch
     out = policy.sample(logits, seed=7, step=env.steps_done)
+
+    from pikazoo_amd import ppo                        # the PPO update loss: loss, statistics and gradients, one pass
+    loss, stats = ppo.loss(logits, values, actions, old_log_probs, advantages, returns)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` on first use: importing the package (and with it the step path) never
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` on first use: importing the package (and with it the step path) never
     # loads those libraries
-    if name in ("learn", "policy"):
+    if name in ("learn", "policy", "ppo"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
