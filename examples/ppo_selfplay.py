@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""Self-play PPO on the project's own pieces: one shared actor-critic plays both sides.
+
+    python pika-zoo_amd/build.py        # once: hipcc --offload-arch=gfx950
+    python examples/ppo_selfplay.py --num-envs 4096 --iters 20 --steps 32
+
+Per policy step: ``ActorCritic.act`` (the net's forward, both agents, one launch) -> ``policy.sample`` (action, log-prob
+and entropy, one launch) -> ``env.step``.  Per iteration: ``learn.gae`` (one launch), then minibatches through
+``ActorCritic.forward`` (torch autograd on the same parameters) -> ``ppo.loss(head=...)`` (loss and gradients in one pass)
+-> ``backward`` -> ``torch.optim.Adam``.  The rollout net reads the parameters in place: nothing to copy after a step of
+the optimizer.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
+
+from pikazoo_amd import learn, net, pikazoo_v0, policy, ppo  # noqa: E402
+from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
+
+
+def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print):
+    """Returns the loss of every minibatch update, as floats."""
+    torch.manual_seed(seed)
+    env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
+    agents = env.agents
+    A = env.action_space(agents[0]).n
+    obs, _ = env.reset()
+    K = obs[agents[0]].shape[1]
+    model = net.ActorCritic(in_features=K, hidden=64, num_actions=A).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
+
+    n, k = num_envs, steps
+    buf_obs = {a: torch.empty((k, n, K), dtype=obs[a].dtype, device=device) for a in agents}
+    buf_act = {a: torch.empty((k, n), dtype=torch.int64, device=device) for a in agents}
+    buf_logp = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
+    buf_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
+    buf_rew = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
+    buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
+    head = picked = targets = None
+    losses, policy_step = [], 0
+
+    for it in range(iters):
+        # ---- rollout: k policy steps, three launches each (net, head, step) ------------------------------------------------
+        for t in range(k):
+            head = model.act(obs, out=head)                       # {agent: [n, A + 1]}: logits and value
+            picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
+            for a in agents:
+                buf_obs[a][t].copy_(obs[a])
+                buf_act[a][t].copy_(picked["actions"][a])
+                buf_logp[a][t].copy_(picked["log_probs"][a])
+                buf_val[a][t].copy_(head[a][:, A])
+            obs, rewards, terminations, _, _ = env.step(picked["actions"])
+            for a in agents:
+                buf_rew[a][t].copy_(rewards[a])
+            buf_term[t].copy_(terminations[agents[0]])
+            policy_step += 1
+        head = model.act(obs, out=head)                           # the bootstrap value
+        for a in agents:
+            buf_val[a][k].copy_(head[a][:, A])
+        targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
+
+        # ---- update: both agents' samples through the one net ----------------------------------------------------------------
+        flat = lambda d: {a: d[a][:k].reshape(k * n, *d[a].shape[2:]) for a in agents}  # noqa: E731
+        f_obs, f_act, f_logp = flat(buf_obs), flat(buf_act), flat(buf_logp)
+        f_adv, f_ret = flat(targets["advantages"]), flat(targets["returns"])
+        size = k * n // minibatches
+        for _ in range(epochs):
+            order = torch.randperm(k * n, device=device)
+            for m in range(minibatches):
+                idx = order[m * size:(m + 1) * size]
+                pick = lambda d: {a: d[a][idx] for a in agents}  # noqa: E731
+                out = {a: model(f_obs[a][idx]) for a in agents}   # the torch route: differentiable
+                loss, stats = ppo.loss(head=out, num_actions=A, actions=pick(f_act), old_log_probs=pick(f_logp),
+                                       advantages=pick(f_adv), returns=pick(f_ret), clip=0.2, vf_coef=0.5, ent_coef=0.01)
+                optimizer.zero_grad(set_to_none=True)
+                sum(loss.values()).backward()
+                torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+                optimizer.step()
+                losses.append(sum(loss.values()).detach())
+        log(f"iter {it}: loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][agents[0]]):.3f} | "
+            f"approx_kl {float(stats['approx_kl'][agents[0]]):.5f} | mean reward {float(buf_rew[agents[0]].mean()):+.5f}")
+    return [float(x) for x in losses]
+
+
+if __name__ == "__main__":
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--num-envs", type=int, default=1024)
+    p.add_argument("--iters", type=int, default=4)
+    p.add_argument("--steps", type=int, default=16)
+    args = p.parse_args()
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps)

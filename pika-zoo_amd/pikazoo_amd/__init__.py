@@ -11,16 +11,19 @@
 
     from pikazoo_amd import ppo                        # the PPO update loss: loss, statistics and gradients, one pass
     loss, stats = ppo.loss(logits, values, actions, old_log_probs, advantages, returns)
+
+    from pikazoo_amd import net                        # the policy net's forward: observations -> [N, A + 1] head, one launch
+    head = net.ActorCritic().to("cuda").act(obs)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` on first use: importing the package (and with it the step path) never
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` on first use: importing the package (and with it the step path) never
     # loads those libraries
-    if name in ("learn", "policy", "ppo"):
+    if name in ("learn", "policy", "ppo", "net"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
