@@ -6,9 +6,10 @@
 
 Per policy step: ``ActorCritic.act`` (the net's forward, both agents, one launch) -> ``policy.sample`` (action, log-prob
 and entropy, one launch) -> ``env.step``.  Per iteration: ``learn.gae`` (one launch), then minibatches through
-``ActorCritic.forward`` (torch autograd on the same parameters) -> ``ppo.loss(head=...)`` (loss and gradients in one pass)
--> ``backward`` -> ``torch.optim.Adam``.  The rollout net reads the parameters in place: nothing to copy after a step of
-the optimizer.
+``ActorCritic.evaluate`` (the same forward launch, differentiable, both agents at once) -> ``ppo.loss(head=...)`` (loss and
+gradients in one pass) -> ``backward`` (``netgrad.backward``: the six parameter gradients in one call) ->
+``torch.optim.Adam``.  ``--torch-update`` (``native_update=False``) keeps the update on ``ActorCritic.forward`` and torch
+autograd.  The rollout net reads the parameters in place: nothing to copy after a step of the optimizer.
 """
 import argparse
 import sys
@@ -22,7 +23,8 @@ from pikazoo_amd import learn, net, pikazoo_v0, policy, ppo  # noqa: E402
 from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
-def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print):
+def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
+         native_update=True):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -73,7 +75,10 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
             for m in range(minibatches):
                 idx = order[m * size:(m + 1) * size]
                 pick = lambda d: {a: d[a][idx] for a in agents}  # noqa: E731
-                out = {a: model(f_obs[a][idx]) for a in agents}   # the torch route: differentiable
+                if native_update:
+                    out = model.evaluate(pick(f_obs))             # one forward launch; its backward is one call
+                else:
+                    out = {a: model(f_obs[a][idx]) for a in agents}   # the torch route: differentiable
                 loss, stats = ppo.loss(head=out, num_actions=A, actions=pick(f_act), old_log_probs=pick(f_logp),
                                        advantages=pick(f_adv), returns=pick(f_ret), clip=0.2, vf_coef=0.5, ent_coef=0.01)
                 optimizer.zero_grad(set_to_none=True)
@@ -91,5 +96,6 @@ if __name__ == "__main__":
     p.add_argument("--num-envs", type=int, default=1024)
     p.add_argument("--iters", type=int, default=4)
     p.add_argument("--steps", type=int, default=16)
+    p.add_argument("--torch-update", action="store_true", help="update through ActorCritic.forward and torch autograd")
     args = p.parse_args()
-    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps)
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update)

@@ -1,5 +1,5 @@
 """Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so, libpikazoo_learn.so, libpikazoo_policy.so,
-libpikazoo_ppo.so and libpikazoo_net.so -- for gfx950 with hipcc (in-tree, no JIT cache).
+libpikazoo_ppo.so, libpikazoo_net.so and libpikazoo_netgrad.so -- for gfx950 with hipcc (in-tree, no JIT cache).
 
     python pika-zoo_amd/build.py [--force]
 
@@ -11,8 +11,9 @@ loaded by bench.py and tests/ only (pika-zoo_amd/diag.py); it carries the same b
 product library holds none of it.  The policy library (include/pikazoo_policy.h: pz_sample_actions, pz_action_log_probs and
 its backward) is a fourth, bound by pikazoo_amd/policy.py; the PPO library (include/pikazoo_ppo.h: pz_ppo_moments, pz_ppo_loss)
 a fifth, bound by pikazoo_amd/ppo.py, which shares csrc/pz_policy_rows.hpp with the fourth; the net library
-(include/pikazoo_net.h: pz_mlp_forward) a sixth, bound by pikazoo_amd/net.py.  The six compiles are independent and run side by
-side.
+(include/pikazoo_net.h: pz_mlp_forward) a sixth, bound by pikazoo_amd/net.py; the net-gradient library
+(include/pikazoo_netgrad.h: pz_mlp_backward) a seventh, bound by pikazoo_amd/netgrad.py.  The seven compiles are independent and
+run side by side.
 """
 from __future__ import annotations
 
@@ -34,16 +35,18 @@ LEARN_LIB = LIB_DIR / "libpikazoo_learn.so"
 POLICY_LIB = LIB_DIR / "libpikazoo_policy.so"
 PPO_LIB = LIB_DIR / "libpikazoo_ppo.so"
 NET_LIB = LIB_DIR / "libpikazoo_net.so"
+NETGRAD_LIB = LIB_DIR / "libpikazoo_netgrad.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
 LEARN_SOURCES = [CSRC / "pz_learn.hip"]
 POLICY_SOURCES = [CSRC / "pz_policy.hip"]
 PPO_SOURCES = [CSRC / "pz_ppo.hip"]
 NET_SOURCES = [CSRC / "pz_net.hip"]
-DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + POLICY_SOURCES + PPO_SOURCES + NET_SOURCES + [
+NETGRAD_SOURCES = [CSRC / "pz_netgrad.hip"]
+DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + POLICY_SOURCES + PPO_SOURCES + NET_SOURCES + NETGRAD_SOURCES + [
     CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
     CSRC / "pz_policy_rows.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
-    INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h"]
+    INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
@@ -86,7 +89,7 @@ def library_id(lib: Path = LIB):
 
 
 def needs_build() -> bool:
-    return any(library_id(lib) != source_id() for lib in (LIB, DIAG_LIB, LEARN_LIB, POLICY_LIB, PPO_LIB, NET_LIB))
+    return any(library_id(lib) != source_id() for lib in (LIB, DIAG_LIB, LEARN_LIB, POLICY_LIB, PPO_LIB, NET_LIB, NETGRAD_LIB))
 
 
 def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
@@ -101,9 +104,9 @@ def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
-    """The product library (returned) with the diagnostics, the learning, the policy, the PPO and the net library beside it: each is compiled
+    """The product library (returned) with the diagnostics, the learning, the policy, the PPO, the net and the net-gradient library beside it: each is compiled
     when it is missing or stale, the compiles side by side (a cold build takes about as long as the product library alone:
-    some three minutes; an up-to-date tree costs six file reads)."""
+    some three minutes; an up-to-date tree costs seven file reads)."""
     if any("PZ_DIAGNOSTIC_BUILD" in f for f in extra_flags):
         # csrc/pz_diagnostic.hpp: the one compile-time switch of the kernels -- tools/ab.py builds such variants into
         # tools/bin/; the product path never holds one (and _native.load() would refuse its build id "diagnostic")
@@ -111,7 +114,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
     want = source_id(tuple(extra_flags))
     LIB_DIR.mkdir(parents=True, exist_ok=True)
     todo = [(out, sources) for out, sources in ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES),
-                                                (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES), (NET_LIB, NET_SOURCES))
+                                                (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES), (NET_LIB, NET_SOURCES),
+                                                (NETGRAD_LIB, NETGRAD_SOURCES))
             if force or extra_flags or library_id(out) != want]
     if len(todo) > 1:
         from concurrent.futures import ThreadPoolExecutor

@@ -14,16 +14,19 @@
 
     from pikazoo_amd import net                        # the policy net's forward: observations -> [N, A + 1] head, one launch
     head = net.ActorCritic().to("cuda").act(obs)
+
+    from pikazoo_amd import netgrad                    # the policy net's backward: d loss / d head -> six parameter gradients
+    grads = netgrad.backward(obs, params, grad_head)   # (or model.evaluate(obs) and torch's own .backward())
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` on first use: importing the package (and with it the step path) never
-    # loads those libraries
-    if name in ("learn", "policy", "ppo", "net"):
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` on first use: importing
+    # the package (and with it the step path) never loads those libraries
+    if name in ("learn", "policy", "ppo", "net", "netgrad"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

@@ -231,9 +231,10 @@ class ActorCritic(torch.nn.Module):
     head shared between the policy and the value; column ``num_actions`` of the output is the value.  Orthogonal weights
     with the gains sqrt 2, sqrt 2 and 0.01, biases 0.
 
-    ``forward(obs)`` is the torch route, differentiable: the update side.  ``act(obs)`` is :func:`forward` of this module
-    (one launch, no graph): the rollout side.  Both read the same storage, so there is nothing to synchronise after
-    ``optimizer.step()``."""
+    ``forward(obs)`` is the torch route, differentiable.  ``act(obs)`` is :func:`forward` of this module (one launch, no
+    graph): the rollout side.  ``evaluate(obs)`` is the same launch made differentiable by ``netgrad.head``: the update side,
+    one call forward and one call backward for both agents.  All read the same storage, so there is nothing to synchronise
+    after ``optimizer.step()``."""
 
     def __init__(self, in_features: int = 35, hidden: int = 64, num_actions: int = 18, activation: str = "tanh"):
         super().__init__()
@@ -267,3 +268,11 @@ class ActorCritic(torch.nn.Module):
         this module's parameters, in one launch"""
         with torch.no_grad():
             return forward(obs, self.parameter_tensors(), self.activation, out=out, out_dtype=out_dtype)
+
+    def evaluate(self, obs):
+        """the ``[N, num_actions + 1]`` float32 head of a tensor or an ``{agent: tensor}`` dict of observations, as
+        :meth:`act` computes it, differentiable with respect to this module's parameters: ``netgrad.head`` (imported on
+        first use: nothing loads libpikazoo_netgrad.so before), whose backward is one ``netgrad.backward`` call"""
+        from . import netgrad
+
+        return netgrad.head(obs, self.parameter_tensors(), self.activation)

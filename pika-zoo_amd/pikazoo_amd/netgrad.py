@@ -1,0 +1,264 @@
+"""The step of a PPO update that follows ``ppo.loss(head=...)``: from ``d loss / d head`` to the six parameter gradients of
+``net``'s three-layer policy net, in ONE call, the forward recomputed inside it.
+
+    from pikazoo_amd import net, netgrad, ppo
+    model = net.ActorCritic(in_features=35, hidden=64, num_actions=18).to("cuda")
+    head = model.evaluate(obs)                    # net.forward, differentiable: one launch for both agents
+    loss = ...(head)                              # anything torch can differentiate, or ppo.loss(head=head)
+    loss.backward()                               # netgrad.backward: the .grad of the six parameters, one call
+
+    grads = netgrad.backward(obs, model.parameter_tensors(), grad_head)       # the same without autograd
+
+ctypes binding of libpikazoo_netgrad.so (C ABI and the definition: include/pikazoo_netgrad.h), a library of its own beside the
+product library; nothing in the step path, ``learn``, ``policy``, ``ppo`` or ``net`` imports this module.  There is no torch
+fallback: a missing or stale library raises.  Operands and accumulation are float32; the sums over the rows are
+deterministic (no atomics): two calls on the same inputs return the same bits.  Hidden widths 32, 64 and 128: the whole box
+of ``net.forward``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _native, net
+
+LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_netgrad.so"
+ABI_VERSION = 1
+GRAD_FORMATS = net.OUT_FORMATS
+NAMES = ("W1", "b1", "W2", "b2", "W3", "b3")
+
+_P = C.c_void_p
+SIGNATURES = {
+    "pz_netgrad_abi_version": (C.c_int, []),
+    "pz_netgrad_build_id": (C.c_char_p, []),
+    # (n, in_features, hidden, out_features)
+    "pz_mlp_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    # (obs_p1, obs_p2, obs_format, n, in_features, obs_pitch, hidden, out_features, activation, six parameters of agent 1, six of
+    #  agent 2, grad_head_p1, grad_head_p2, grad_format, grad_pitch, six gradients of agent 1, six of agent 2, workspace, stream)
+    "pz_mlp_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [_P] * 12
+                        + [_P, _P, C.c_int32, C.c_int64] + [_P] * 12 + [_P, _P]),
+}
+_ERRORS = {-1: "a required pointer is NULL", -2: "a size or a pitch beyond the kernel's range",
+           -3: "an unknown format or activation, or a shared net on two parameter sets", -4: "a pointer not aligned to its element"}
+_lib = None
+
+
+def load():
+    """Load libpikazoo_netgrad.so (once).  Raises if it has not been built or was built from other sources than the ones in
+    this tree."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not LIB_PATH.exists():
+        raise _native.PikazooNativeError(
+            f"{LIB_PATH} is missing: build it with `python pika-zoo_amd/build.py` (hipcc --offload-arch=gfx950). "
+            "There is no torch fallback.")
+    if (_native.PKG_ROOT / "csrc" / "pz_netgrad.hip").exists():  # a source tree: the library must match it
+        b = _native._pz_build()
+        have, want = b.library_id(LIB_PATH), b.source_id()
+        if have != want:
+            raise _native.PikazooNativeError(
+                f"{LIB_PATH} is stale: built from sources {have}, the tree holds {want}; rebuild it with "
+                "`python pika-zoo_amd/build.py`")
+    lib = C.CDLL(str(LIB_PATH))
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the export is missing
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.pz_netgrad_abi_version() != ABI_VERSION:
+        raise _native.PikazooNativeError(f"ABI mismatch: library {lib.pz_netgrad_abi_version()} != binding {ABI_VERSION}")
+    _lib = lib
+    return lib
+
+
+def rows_per_pass(hidden: int) -> int:
+    """the rows a workgroup takes at a time (include/pikazoo_netgrad.h)"""
+    return 32 * (128 // hidden)
+
+
+def workspace_bytes(n: int, in_features: int, hidden: int, out_features: int, device=None) -> int:
+    """``pz_mlp_backward_workspace_bytes`` restated, so that a workspace is sized and checked before the library is needed:
+    two agents x min(passes, compute units of ``device``) partial sums of all six gradients.  0 outside the box."""
+    if not (0 < n <= 1 << 30 and 1 <= in_features <= net.MAX_IN and hidden in net.HIDDEN and 1 <= out_features <= net.MAX_OUT):
+        return 0
+    dev = torch.device(device) if device is not None else None
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev is not None and dev.type == "cuda" else 256
+    passes = -(-n // rows_per_pass(hidden))
+    floats = hidden * in_features + hidden + hidden * hidden + hidden + out_features * hidden + out_features
+    return 2 * min(passes, cus) * floats * 4
+
+
+def workspace(n: int, in_features: int, hidden: int, out_features: int, device) -> torch.Tensor:
+    """a workspace for :func:`backward` on up to ``n`` rows per agent"""
+    return torch.empty(max(workspace_bytes(n, in_features, hidden, out_features, device), 16), dtype=torch.uint8, device=device)
+
+
+def _six(seq, what):
+    if isinstance(seq, torch.Tensor) or not hasattr(seq, "__len__") or len(seq) != 6:
+        raise ValueError(f"{what} must be a sequence of six tensors (dW1, db1, dW2, db2, dW3, db3)")
+    for t in seq:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: a gradient must be a tensor, got {type(t).__name__}")
+    return list(seq)
+
+
+def backward(obs, params, grad_head, activation: str = "tanh", out=None, workspace=None, shared=None):
+    """The six parameter gradients of ``net.forward(obs, params)`` under ``grad_head = d loss / d head``, in one call
+    (``pz_mlp_backward``: two launches whatever N is).  The definition is include/pikazoo_netgrad.h's.
+
+    ``obs`` and ``params`` are :func:`net.forward`'s, convention for convention: a tensor or an ``{agent: tensor}`` dict of
+    one or two agents; one parameter sequence or an ``{agent: ...}`` dict of them.  ``grad_head``: ``[N, O]`` float32,
+    float16 or bfloat16 in the shape of ``obs`` (tensor or dict), at any common row stride >= O, the last dimension
+    contiguous -- what ``ppo.loss(head=...)`` returns.
+
+    One sequence given with a two-agent ``obs`` means a SHARED net: the gradients of both agents' rows are summed (agent 1's
+    sum plus agent 2's) and come back as one tuple of six.  ``shared=True`` asks for that explicitly (a dict must then hold
+    the same six tensors twice); ``shared=False`` returns ``{agent: tuple of six}`` even for one sequence.  Otherwise the
+    result has the shape of ``params``: a tuple of six float32 tensors with the parameters' shapes, or a dict of them.
+
+    ``out=`` (a previous result) and ``workspace=`` (:func:`workspace`) make the call allocation-free.  Outputs are
+    overwritten, not accumulated into, and must not overlap an input, the workspace or each other.  The launches go to the
+    current stream without a synchronisation.  Shape, dtype, stride, alias and range errors raise ``ValueError`` before the
+    library is needed."""
+    keys, xs = net._sides(obs, "obs")
+    x0 = xs[0]
+    if x0.dim() != 2:
+        raise ValueError(f"obs must have shape [N, K], got {tuple(x0.shape)}")
+    n, K, dev = int(x0.shape[0]), int(x0.shape[1]), x0.device
+    if not 1 <= K <= net.MAX_IN:
+        raise ValueError(f"obs: 1 <= K <= {net.MAX_IN} features, got {K}")
+    if n > 1 << 30:
+        raise ValueError(f"obs: at most 2^30 rows, got {n}")
+    if x0.dtype not in net.OBS_FORMATS:
+        raise ValueError(f"obs must be {' or '.join(str(d) for d in net.OBS_FORMATS)}, got {x0.dtype}")
+    obs_pitch = net._rows(xs, "obs", n, K, tuple(net.OBS_FORMATS), dev)
+    if activation not in net.ACTIVATIONS:
+        raise ValueError(f"activation must be {' or '.join(repr(a) for a in net.ACTIVATIONS)}, got {activation!r}")
+    sets = net._parameter_sets(params, keys, len(xs))
+    w1 = sets[0][0]
+    if w1.dim() != 2:
+        raise ValueError(f"W1 must have shape [hidden, {K}], got {tuple(w1.shape)}")
+    H = int(w1.shape[0])
+    if H not in net.HIDDEN:
+        raise ValueError(f"hidden must be one of {net.HIDDEN}, got {H}")
+    w3 = sets[0][4]
+    if w3.dim() != 2:
+        raise ValueError(f"W3 must have shape [out_features, {H}], got {tuple(w3.shape)}")
+    O = int(w3.shape[0])
+    if not 1 <= O <= net.MAX_OUT:
+        raise ValueError(f"1 <= out_features <= {net.MAX_OUT}, got {O}")
+    shapes = ((H, K), (H,), (H, H), (H,), (O, H), (O,))
+    for ps in sets:
+        for name, shape, p in zip(NAMES, shapes, ps):
+            if tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {p.dtype} {list(p.shape)} on "
+                                 f"{p.device}{'' if p.is_contiguous() else ', not contiguous'}")
+    gkeys, gs = net._sides(grad_head, "grad_head")
+    if gkeys != keys:
+        raise ValueError(f"grad_head must name the agents of obs in their order: {keys}, got {gkeys}")
+    if gs[0].dtype not in GRAD_FORMATS:
+        raise ValueError(f"grad_head must be {' or '.join(str(d) for d in GRAD_FORMATS)}, got {gs[0].dtype}")
+    grad_pitch = net._rows(gs, "grad_head", n, O, tuple(GRAD_FORMATS), dev)
+    # shared or separate
+    if shared is None:
+        shared = len(xs) == 2 and not isinstance(params, dict)
+    shared = bool(shared)
+    if shared and len(xs) != 2:
+        raise ValueError("shared=True needs two agents")
+    if shared and any(p.data_ptr() != q.data_ptr() for p, q in zip(*sets)):
+        raise ValueError("shared=True: both agents must name the same six parameter tensors")
+    groups = 1 if shared else len(xs)
+    if out is not None:
+        if groups == 1 and (keys is None or shared):
+            outs = [_six(out, "out")]
+        else:
+            if not isinstance(out, dict) or list(out) != keys:
+                raise ValueError(f"out must name the agents of obs in their order: {keys}")
+            outs = [_six(o, "out") for o in out.values()]
+        for os_ in outs:
+            for name, shape, t in zip(NAMES, shapes, os_):
+                if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"out: d{name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {t.dtype} "
+                                     f"{list(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+    need = workspace_bytes(n, K, H, O, dev)
+    if workspace is not None:
+        ws = workspace
+        if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.device != dev
+                or ws.numel() < need or ws.data_ptr() % 16):
+            raise ValueError(f"the workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}, aligned to 16")
+    if dev.type != "cuda":
+        raise ValueError(f"the policy net runs on the GPU: obs are on {dev}")
+    if out is None:
+        outs = [[torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes] for _ in range(groups)]
+    if workspace is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    inputs = ([(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"grad_head[{s}]", g) for s, g in enumerate(gs)]
+              + [(f"{name}[{s}]", p) for s, ps in enumerate(sets) for name, p in zip(NAMES, ps)])
+    net._no_alias([(f"out[{s}].d{name}", t) for s, os_ in enumerate(outs) for name, t in zip(NAMES, os_)] + [("workspace", ws)], inputs)
+    if groups == 1 and (keys is None or shared):
+        result = tuple(outs[0])
+    else:
+        result = {k: tuple(o) for k, o in zip(keys, outs)}
+    if n == 0:  # nothing to sum: the gradients of no rows
+        for os_ in outs:
+            for t in os_:
+                t.zero_()
+        return result
+    lib = load()
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    two = len(xs) == 2
+    with torch.cuda.device(index):
+        if lib.pz_mlp_backward_workspace_bytes(n, K, H, O) > ws.numel():
+            raise _native.PikazooNativeError("the workspace is smaller than pz_mlp_backward_workspace_bytes asks for")
+        stream = net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
+        code = lib.pz_mlp_backward(
+            xs[0].data_ptr(), xs[1].data_ptr() if two else None, net.OBS_FORMATS[x0.dtype], n, K, obs_pitch, H, O,
+            net.ACTIVATIONS[activation], *[p.data_ptr() for p in sets[0]], *([p.data_ptr() for p in sets[1]] if two else [None] * 6),
+            gs[0].data_ptr(), gs[1].data_ptr() if two else None, GRAD_FORMATS[gs[0].dtype], grad_pitch,
+            *[t.data_ptr() for t in outs[0]], *([t.data_ptr() for t in outs[1]] if groups == 2 else [None] * 6), ws.data_ptr(), stream)
+    if code != 0:
+        raise _native.PikazooNativeError(f"pz_mlp_backward failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+    return result
+
+
+class _Head(torch.autograd.Function):
+    """``net.forward`` with ``netgrad.backward`` behind it: (activation, number of agents, obs..., six parameters) -> heads"""
+
+    @staticmethod
+    def forward(ctx, activation, sides, *tensors):
+        xs, params = tensors[:sides], tensors[sides:]
+        ctx.activation, ctx.sides = activation, sides
+        ctx.save_for_backward(*tensors)
+        x = xs[0] if sides == 1 else {s: t for s, t in enumerate(xs)}
+        y = net.forward(x, [p.detach() for p in params], activation)
+        return (y,) if sides == 1 else tuple(y.values())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        sides = ctx.sides
+        tensors = ctx.saved_tensors
+        xs, params = tensors[:sides], tensors[sides:]
+        n, O = int(xs[0].shape[0]), int(params[4].shape[0])
+        gs = [torch.zeros((n, O), dtype=torch.float32, device=xs[0].device) if g is None else g for g in grads]
+        plain = all(g.dim() == 2 and (O == 1 or g.stride(1) == 1) and (n <= 1 or g.stride(0) >= O) for g in gs)
+        if not plain or len({g.stride(0) for g in gs}) != 1 or len({g.dtype for g in gs}) != 1:
+            gs = [g.to(torch.float32).contiguous() for g in gs]
+        x = xs[0] if sides == 1 else {s: t for s, t in enumerate(xs)}
+        g = gs[0] if sides == 1 else {s: t for s, t in enumerate(gs)}
+        out = backward(x, [p.detach() for p in params], g, ctx.activation)
+        return (None, None) + (None,) * sides + tuple(out)
+
+
+def head(obs, params, activation: str = "tanh"):
+    """``net.forward(obs, params)`` (float32) as a differentiable function of the six parameters: one forward launch, and one
+    :func:`backward` call when autograd walks back through it.  ``obs`` is a tensor or an ``{agent: tensor}`` dict of one or
+    two agents on ONE parameter sequence (a shared net: the gradients of both agents' rows are summed).  ``obs`` gets no
+    gradient.  An incoming gradient that is ``None`` counts as zeros; one whose last dimension is not contiguous or whose
+    rows overlap (``expand``) is made contiguous first."""
+    keys, xs = net._sides(obs, "obs")
+    if isinstance(params, dict) or isinstance(params, torch.Tensor) or not hasattr(params, "__len__") or len(params) != 6:
+        raise ValueError("params must be one sequence of six tensors (W1, b1, W2, b2, W3, b3)")
+    ys = _Head.apply(activation, len(xs), *xs, *params)
+    return dict(zip(keys, ys)) if keys is not None else ys[0]
