@@ -8,8 +8,10 @@ Per policy step: ``ActorCritic.act`` (the net's forward, both agents, one launch
 and entropy, one launch) -> ``env.step``.  Per iteration: ``learn.gae`` (one launch), then minibatches through
 ``ActorCritic.evaluate`` (the same forward launch, differentiable, both agents at once) -> ``ppo.loss(head=...)`` (loss and
 gradients in one pass) -> ``backward`` (``netgrad.backward``: the six parameter gradients in one call) ->
-``torch.optim.Adam``.  ``--torch-update`` (``native_update=False``) keeps the update on ``ActorCritic.forward`` and torch
-autograd.  The rollout net reads the parameters in place: nothing to copy after a step of the optimizer.
+``optim.Adam.step`` (the gradient clip and Adam in one launch).  ``--torch-update`` (``native_update=False``) keeps the update
+on ``ActorCritic.forward`` and torch autograd; ``--torch-optimizer`` (``native_optimizer=False``) keeps
+``clip_grad_norm_`` and ``torch.optim.Adam``.  The rollout net reads the parameters in place: nothing to copy after a step
+of the optimizer.
 """
 import argparse
 import sys
@@ -19,12 +21,12 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
-from pikazoo_amd import learn, net, pikazoo_v0, policy, ppo  # noqa: E402
+from pikazoo_amd import learn, net, optim, pikazoo_v0, policy, ppo  # noqa: E402
 from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True):
+         native_update=True, native_optimizer=True):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -33,7 +35,10 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
     obs, _ = env.reset()
     K = obs[agents[0]].shape[1]
     model = net.ActorCritic(in_features=K, hidden=64, num_actions=A).to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
+    if native_optimizer:
+        optimizer = optim.Adam(model.parameters(), lr=lr, eps=1e-5, max_grad_norm=0.5)   # the clip is part of its launch
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
 
     n, k = num_envs, steps
     buf_obs = {a: torch.empty((k, n, K), dtype=obs[a].dtype, device=device) for a in agents}
@@ -83,7 +88,8 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
                                        advantages=pick(f_adv), returns=pick(f_ret), clip=0.2, vf_coef=0.5, ent_coef=0.01)
                 optimizer.zero_grad(set_to_none=True)
                 sum(loss.values()).backward()
-                torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+                if not native_optimizer:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
                 optimizer.step()
                 losses.append(sum(loss.values()).detach())
         log(f"iter {it}: loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][agents[0]]):.3f} | "
@@ -97,5 +103,7 @@ if __name__ == "__main__":
     p.add_argument("--iters", type=int, default=4)
     p.add_argument("--steps", type=int, default=16)
     p.add_argument("--torch-update", action="store_true", help="update through ActorCritic.forward and torch autograd")
+    p.add_argument("--torch-optimizer", action="store_true", help="clip_grad_norm_ and torch.optim.Adam instead of optim.Adam")
     args = p.parse_args()
-    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update)
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
+         native_optimizer=not args.torch_optimizer)

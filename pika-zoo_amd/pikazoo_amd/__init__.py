@@ -17,16 +17,19 @@
 
     from pikazoo_amd import netgrad                    # the policy net's backward: d loss / d head -> six parameter gradients
     grads = netgrad.backward(obs, params, grad_head)   # (or model.evaluate(obs) and torch's own .backward())
+
+    from pikazoo_amd import optim                      # the optimizer step: gradient clip + Adam / AdamW, one launch
+    optimizer = optim.Adam(model.parameters(), lr=3e-4, max_grad_norm=0.5)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` on first use: importing
-    # the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad"):
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` on first use:
+    # importing the package (and with it the step path) never loads those libraries
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
