@@ -11,7 +11,10 @@ gradients in one pass) -> ``backward`` (``netgrad.backward``: the six parameter 
 ``optim.Adam.step`` (the gradient clip and Adam in one launch).  ``--torch-update`` (``native_update=False``) keeps the update
 on ``ActorCritic.forward`` and torch autograd; ``--torch-optimizer`` (``native_optimizer=False``) keeps
 ``clip_grad_norm_`` and ``torch.optim.Adam``.  The rollout net reads the parameters in place: nothing to copy after a step
-of the optimizer.
+of the optimizer.  ``native_batch=True`` moves the data between these stages with ``batch.RolloutBuffer``: one ``store`` per
+policy step instead of eleven ``copy_`` calls, and one ``minibatch`` per minibatch instead of ``randperm`` and ten index
+gathers.  It is off by default, because what it costs against the torch route is not measured yet:
+``--native-batch`` turns it on.
 """
 import argparse
 import sys
@@ -21,12 +24,12 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
-from pikazoo_amd import learn, net, optim, pikazoo_v0, policy, ppo  # noqa: E402
+from pikazoo_amd import batch, learn, net, optim, pikazoo_v0, policy, ppo  # noqa: E402
 from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True, native_optimizer=True):
+         native_update=True, native_optimizer=True, native_batch=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -41,12 +44,14 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
         optimizer = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
 
     n, k = num_envs, steps
-    buf_obs = {a: torch.empty((k, n, K), dtype=obs[a].dtype, device=device) for a in agents}
-    buf_act = {a: torch.empty((k, n), dtype=torch.int64, device=device) for a in agents}
-    buf_logp = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
-    buf_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
-    buf_rew = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
-    buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
+    buf = gathered = rewards = terminations = None   # native_batch: the buffers take their shapes from the first policy step
+    if not native_batch:
+        buf_obs = {a: torch.empty((k, n, K), dtype=obs[a].dtype, device=device) for a in agents}
+        buf_act = {a: torch.empty((k, n), dtype=torch.int64, device=device) for a in agents}
+        buf_logp = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
+        buf_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
+        buf_rew = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
+        buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
     head = picked = targets = None
     losses, policy_step = [], 0
 
@@ -55,35 +60,58 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
         for t in range(k):
             head = model.act(obs, out=head)                       # {agent: [n, A + 1]}: logits and value
             picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
-            for a in agents:
-                buf_obs[a][t].copy_(obs[a])
-                buf_act[a][t].copy_(picked["actions"][a])
-                buf_logp[a][t].copy_(picked["log_probs"][a])
-                buf_val[a][t].copy_(head[a][:, A])
+            if native_batch:
+                if buf is None:
+                    buf = batch.RolloutBuffer(k, n, dict(obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head),
+                                              minibatches=minibatches, seed=seed)
+                # one launch: this step's records to row t, the outcome of the previous step (what came with obs) to row t - 1
+                buf.store(t, obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head,
+                          rewards=rewards if t else None, terminations=terminations if t else None)
+            else:
+                for a in agents:
+                    buf_obs[a][t].copy_(obs[a])
+                    buf_act[a][t].copy_(picked["actions"][a])
+                    buf_logp[a][t].copy_(picked["log_probs"][a])
+                    buf_val[a][t].copy_(head[a][:, A])
             obs, rewards, terminations, _, _ = env.step(picked["actions"])
-            for a in agents:
-                buf_rew[a][t].copy_(rewards[a])
-            buf_term[t].copy_(terminations[agents[0]])
+            if not native_batch:
+                for a in agents:
+                    buf_rew[a][t].copy_(rewards[a])
+                buf_term[t].copy_(terminations[agents[0]])
             policy_step += 1
         head = model.act(obs, out=head)                           # the bootstrap value
-        for a in agents:
-            buf_val[a][k].copy_(head[a][:, A])
-        targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
+        if native_batch:
+            buf.store(k, head=head, rewards=rewards, terminations=terminations)
+            targets = learn.gae(buf.rewards, buf.values, buf.terminations, gamma=0.99, lam=0.95, out=targets)
+            buf.set_targets(targets)
+        else:
+            for a in agents:
+                buf_val[a][k].copy_(head[a][:, A])
+            targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
 
         # ---- update: both agents' samples through the one net ----------------------------------------------------------------
         flat = lambda d: {a: d[a][:k].reshape(k * n, *d[a].shape[2:]) for a in agents}  # noqa: E731
-        f_obs, f_act, f_logp = flat(buf_obs), flat(buf_act), flat(buf_logp)
-        f_adv, f_ret = flat(targets["advantages"]), flat(targets["returns"])
+        if not native_batch:
+            f_obs, f_act, f_logp = flat(buf_obs), flat(buf_act), flat(buf_logp)
+            f_adv, f_ret = flat(targets["advantages"]), flat(targets["returns"])
         size = k * n // minibatches
-        for _ in range(epochs):
-            order = torch.randperm(k * n, device=device)
+        for epoch in range(epochs):
+            if not native_batch:
+                order = torch.randperm(k * n, device=device)
             for m in range(minibatches):
-                idx = order[m * size:(m + 1) * size]
-                pick = lambda d: {a: d[a][idx] for a in agents}  # noqa: E731
+                if native_batch:
+                    # one launch: minibatch m of the epoch's shuffle, every tensor of both agents (no randperm, no index tensor)
+                    gathered = buf.minibatch(counter=(it * epochs + epoch) * minibatches + m, out=gathered)
+                    pick = lambda d: d  # noqa: E731
+                    f_obs, f_act, f_logp = gathered["obs"], gathered["actions"], gathered["log_probs"]
+                    f_adv, f_ret = gathered["advantages"], gathered["returns"]
+                else:
+                    idx = order[m * size:(m + 1) * size]
+                    pick = lambda d: {a: d[a][idx] for a in agents}  # noqa: E731
                 if native_update:
                     out = model.evaluate(pick(f_obs))             # one forward launch; its backward is one call
                 else:
-                    out = {a: model(f_obs[a][idx]) for a in agents}   # the torch route: differentiable
+                    out = {a: model(pick(f_obs)[a]) for a in agents}   # the torch route: differentiable
                 loss, stats = ppo.loss(head=out, num_actions=A, actions=pick(f_act), old_log_probs=pick(f_logp),
                                        advantages=pick(f_adv), returns=pick(f_ret), clip=0.2, vf_coef=0.5, ent_coef=0.01)
                 optimizer.zero_grad(set_to_none=True)
@@ -93,7 +121,7 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
                 optimizer.step()
                 losses.append(sum(loss.values()).detach())
         log(f"iter {it}: loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][agents[0]]):.3f} | "
-            f"approx_kl {float(stats['approx_kl'][agents[0]]):.5f} | mean reward {float(buf_rew[agents[0]].mean()):+.5f}")
+            f"approx_kl {float(stats['approx_kl'][agents[0]]):.5f} | mean reward {float((buf.rewards if native_batch else buf_rew)[agents[0]].float().mean()):+.5f}")
     return [float(x) for x in losses]
 
 
@@ -104,6 +132,7 @@ if __name__ == "__main__":
     p.add_argument("--steps", type=int, default=16)
     p.add_argument("--torch-update", action="store_true", help="update through ActorCritic.forward and torch autograd")
     p.add_argument("--torch-optimizer", action="store_true", help="clip_grad_norm_ and torch.optim.Adam instead of optim.Adam")
+    p.add_argument("--native-batch", action="store_true", help="batch.RolloutBuffer: one store per policy step, one gather per minibatch")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
-         native_optimizer=not args.torch_optimizer)
+         native_optimizer=not args.torch_optimizer, native_batch=args.native_batch)

@@ -20,16 +20,19 @@
 
     from pikazoo_amd import optim                      # the optimizer step: gradient clip + Adam / AdamW, one launch
     optimizer = optim.Adam(model.parameters(), lr=3e-4, max_grad_norm=0.5)
+
+    from pikazoo_amd import batch                      # rollout-buffer stores and shuffled minibatch gathers, one launch each
+    minibatch = batch.gather(sources, minibatches=4, seed=0, counter=c)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
