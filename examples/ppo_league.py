@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""League PPO on the project's own pieces: the learner plays a pool of its own frozen snapshots, a different one per game.
+
+    python pika-zoo_amd/build.py        # once: hipcc --offload-arch=gfx950
+    python examples/ppo_league.py --num-envs 4096 --iters 20 --steps 32 --pool 8 --snapshot-every 2
+
+``player_1`` of every game is the learner (pool member 0, the live ``net.ActorCritic``).  ``player_2`` of every game is a
+member drawn for that game with ``torch.randint`` over the current pool -- the learner itself or one of its snapshots -- and
+the draw is renewed once per iteration: ``pool.plan`` groups the games by member (one launch), and every policy step is then
+``pool.Snapshots.act`` (ONE launch for both sides, each row through its own member's net) -> ``policy.sample`` -> ``env.step``.
+Every ``--snapshot-every`` iterations ``push()`` freezes the learner's parameters into the next slot of the ring.  The update
+uses ``player_1``'s samples only, through ``ActorCritic.evaluate`` -> ``ppo.loss`` -> ``backward`` -> ``optim.Adam.step``; the
+snapshots have no gradients.  How opponents are drawn (uniformly here) is plain torch in this loop: prioritised sampling or a
+rating would replace the ``randint``.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
+
+from pikazoo_amd import learn, net, optim, pikazoo_v0, policy, pool, ppo  # noqa: E402
+from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
+
+
+def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print, pool_size=8,
+         snapshot_every=2):
+    """Returns the loss of every minibatch update, as floats."""
+    torch.manual_seed(seed)
+    env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
+    learner, opponent = env.agents
+    A = env.action_space(learner).n
+    obs, _ = env.reset()
+    K = obs[learner].shape[1]
+    model = net.ActorCritic(in_features=K, hidden=64, num_actions=A).to(device)
+    optimizer = optim.Adam(model.parameters(), lr=lr, eps=1e-5, max_grad_norm=0.5)
+    league = pool.Snapshots(model, pool_size)
+
+    n, k = num_envs, steps
+    buf_obs = torch.empty((k, n, K), dtype=obs[learner].dtype, device=device)
+    buf_act = torch.empty((k, n), dtype=torch.int64, device=device)
+    buf_logp = torch.empty((k, n), dtype=torch.float32, device=device)
+    buf_val = torch.empty((k + 1, n), dtype=torch.float32, device=device)
+    buf_rew = torch.empty((k, n), dtype=torch.float32, device=device)
+    buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
+    head = picked = targets = None
+    plans = {}                                                    # {pool size: Plan}: a plan is re-used while the pool keeps its size
+    losses, policy_step = [], 0
+
+    for it in range(iters):
+        if it % snapshot_every == 0 and pool_size > 1:
+            league.push()
+        # ---- every game draws its opponent; the games are grouped by member once per iteration -------------------------------
+        members = torch.randint(len(league), (n,), device=device)
+        plan = plans[len(league)] = pool.plan(members, len(league), out=plans.get(len(league)))
+        sides = {learner: None, opponent: plan}                   # the learner's side needs no plan: member 0 everywhere
+
+        # ---- rollout: k policy steps, three launches each (net over the pool, head, step) ---------------------------------
+        for t in range(k):
+            head = league.act(obs, sides, out=head)               # {agent: [n, A + 1]}: each row under its own member
+            picked = policy.sample({a: head[a][:, :A] for a in env.agents}, seed=seed, step=policy_step, out=picked)
+            buf_obs[t].copy_(obs[learner])
+            buf_act[t].copy_(picked["actions"][learner])
+            buf_logp[t].copy_(picked["log_probs"][learner])
+            buf_val[t].copy_(head[learner][:, A])
+            obs, rewards, terminations, _, _ = env.step(picked["actions"])
+            buf_rew[t].copy_(rewards[learner])
+            buf_term[t].copy_(terminations[learner])
+            policy_step += 1
+        head = league.act(obs, sides, out=head)                   # the bootstrap value
+        buf_val[k].copy_(head[learner][:, A])
+        targets = learn.gae({learner: buf_rew}, {learner: buf_val}, buf_term, gamma=0.99, lam=0.95, out=targets)
+
+        # ---- update: the learner's samples only --------------------------------------------------------------------------------
+        flat = lambda t: t[:k].reshape(k * n, *t.shape[2:])  # noqa: E731
+        f_obs, f_act, f_logp = flat(buf_obs), flat(buf_act), flat(buf_logp)
+        f_adv, f_ret = flat(targets["advantages"][learner]), flat(targets["returns"][learner])
+        size = k * n // minibatches
+        for epoch in range(epochs):
+            order = torch.randperm(k * n, device=device)
+            for m in range(minibatches):
+                idx = order[m * size:(m + 1) * size]
+                out = model.evaluate({learner: f_obs[idx]})
+                loss, stats = ppo.loss(head=out, num_actions=A, actions={learner: f_act[idx]}, old_log_probs={learner: f_logp[idx]},
+                                       advantages={learner: f_adv[idx]}, returns={learner: f_ret[idx]}, clip=0.2, vf_coef=0.5, ent_coef=0.01)
+                optimizer.zero_grad(set_to_none=True)
+                loss[learner].backward()
+                optimizer.step()
+                losses.append(loss[learner].detach())
+        log(f"iter {it}: pool {len(league)} | loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][learner]):.3f} | "
+            f"approx_kl {float(stats['approx_kl'][learner]):.5f} | mean reward {float(buf_rew.mean()):+.5f}")
+    return [float(x) for x in losses]
+
+
+if __name__ == "__main__":
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--num-envs", type=int, default=1024)
+    p.add_argument("--iters", type=int, default=4)
+    p.add_argument("--steps", type=int, default=16)
+    p.add_argument("--pool", type=int, default=8, help="pool members: the learner and pool - 1 snapshots (at most 16)")
+    p.add_argument("--snapshot-every", type=int, default=2, help="iterations between two snapshots of the learner")
+    args = p.parse_args()
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every)

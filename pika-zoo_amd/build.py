@@ -1,5 +1,5 @@
 """Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so, libpikazoo_learn.so, libpikazoo_policy.so,
-libpikazoo_ppo.so, libpikazoo_net.so, libpikazoo_netgrad.so, libpikazoo_optim.so and libpikazoo_batch.so -- for gfx950 with hipcc (in-tree, no JIT cache).
+libpikazoo_ppo.so, libpikazoo_net.so, libpikazoo_netgrad.so, libpikazoo_optim.so, libpikazoo_batch.so and libpikazoo_pool.so -- for gfx950 with hipcc (in-tree, no JIT cache).
 
     python pika-zoo_amd/build.py [--force]
 
@@ -14,8 +14,9 @@ a fifth, bound by pikazoo_amd/ppo.py, which shares csrc/pz_policy_rows.hpp with 
 (include/pikazoo_net.h: pz_mlp_forward) a sixth, bound by pikazoo_amd/net.py; the net-gradient library
 (include/pikazoo_netgrad.h: pz_mlp_backward) a seventh, bound by pikazoo_amd/netgrad.py; the optimizer library
 (include/pikazoo_optim.h: pz_adam_step) an eighth, bound by pikazoo_amd/optim.py; the batch library
-(include/pikazoo_batch.h: pz_batch_copy, pz_batch_gather) a ninth, bound by pikazoo_amd/batch.py.  The nine compiles are
-independent and run side by side.
+(include/pikazoo_batch.h: pz_batch_copy, pz_batch_gather) a ninth, bound by pikazoo_amd/batch.py; the pool library
+(include/pikazoo_pool.h: pz_pool_plan, pz_mlp_forward_pool) a tenth, bound by pikazoo_amd/pool.py, whose tile code
+(csrc/pz_pool_tile.hpp) restates the sixth's.  The ten compiles are independent and run side by side.
 """
 from __future__ import annotations
 
@@ -40,6 +41,7 @@ NET_LIB = LIB_DIR / "libpikazoo_net.so"
 NETGRAD_LIB = LIB_DIR / "libpikazoo_netgrad.so"
 OPTIM_LIB = LIB_DIR / "libpikazoo_optim.so"
 BATCH_LIB = LIB_DIR / "libpikazoo_batch.so"
+POOL_LIB = LIB_DIR / "libpikazoo_pool.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
 LEARN_SOURCES = [CSRC / "pz_learn.hip"]
@@ -49,11 +51,12 @@ NET_SOURCES = [CSRC / "pz_net.hip"]
 NETGRAD_SOURCES = [CSRC / "pz_netgrad.hip"]
 OPTIM_SOURCES = [CSRC / "pz_optim.hip"]
 BATCH_SOURCES = [CSRC / "pz_batch.hip"]
-DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + POLICY_SOURCES + PPO_SOURCES + NET_SOURCES + NETGRAD_SOURCES + OPTIM_SOURCES + BATCH_SOURCES + [
+POOL_SOURCES = [CSRC / "pz_pool.hip"]
+DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + POLICY_SOURCES + PPO_SOURCES + NET_SOURCES + NETGRAD_SOURCES + OPTIM_SOURCES + BATCH_SOURCES + POOL_SOURCES + [
     CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
-    CSRC / "pz_policy_rows.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
+    CSRC / "pz_policy_rows.hpp", CSRC / "pz_pool_tile.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
     INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h",
-    INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h"]
+    INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
@@ -97,7 +100,7 @@ def library_id(lib: Path = LIB):
 
 def needs_build() -> bool:
     return any(library_id(lib) != source_id() for lib in (LIB, DIAG_LIB, LEARN_LIB, POLICY_LIB, PPO_LIB, NET_LIB, NETGRAD_LIB,
-                                                                 OPTIM_LIB, BATCH_LIB))
+                                                                 OPTIM_LIB, BATCH_LIB, POOL_LIB))
 
 
 def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
@@ -112,9 +115,9 @@ def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
-    """The product library (returned) with the diagnostics, the learning, the policy, the PPO, the net, the net-gradient, the optimizer and the batch library beside it: each is compiled
+    """The product library (returned) with the diagnostics, the learning, the policy, the PPO, the net, the net-gradient, the optimizer, the batch and the pool library beside it: each is compiled
     when it is missing or stale, the compiles side by side (a cold build takes about as long as the product library alone:
-    some three minutes; an up-to-date tree costs nine file reads)."""
+    some three minutes; an up-to-date tree costs ten file reads)."""
     if any("PZ_DIAGNOSTIC_BUILD" in f for f in extra_flags):
         # csrc/pz_diagnostic.hpp: the one compile-time switch of the kernels -- tools/ab.py builds such variants into
         # tools/bin/; the product path never holds one (and _native.load() would refuse its build id "diagnostic")
@@ -123,7 +126,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
     LIB_DIR.mkdir(parents=True, exist_ok=True)
     todo = [(out, sources) for out, sources in ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES),
                                                 (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES), (NET_LIB, NET_SOURCES),
-                                                (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES))
+                                                (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES),
+                                                (POOL_LIB, POOL_SOURCES))
             if force or extra_flags or library_id(out) != want]
     if len(todo) > 1:
         from concurrent.futures import ThreadPoolExecutor

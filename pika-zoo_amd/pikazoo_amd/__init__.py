@@ -23,16 +23,19 @@
 
     from pikazoo_amd import batch                      # rollout-buffer stores and shuffled minibatch gathers, one launch each
     minibatch = batch.gather(sources, minibatches=4, seed=0, counter=c)
+
+    from pikazoo_amd import pool                       # the net's forward for a pool of snapshots: each row its own member's net
+    head = pool.Snapshots(model, capacity=8).act(obs, {"player_1": None, "player_2": pool.plan(members, 8)})
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
