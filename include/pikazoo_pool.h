@@ -46,8 +46,8 @@
  *     pz_pool_plan of the same n and P gives unspecified rows, not a fault.
  * THE DEFINITION.  For every valid row i of an agent, out[i] holds exactly the bits that pz_mlp_forward of the same build
  * writes for row i with the parameters of member members[i] (an unplanned agent: member 0).  pikazoo_net.h promises that a
- * row's bits do not depend on the batch, the position or the other agent, so this is well defined; the tile code
- * (csrc/pz_pool_tile.hpp) restates pz_net.hip's operation for operation.  Rows of invalid members, and the columns
+ * row's bits do not depend on the batch, the position or the other agent, so this is well defined; both launches run the
+ * tile code of csrc/pz_mlp_tile.hpp.  Rows of invalid members, and the columns
  * out_features .. out_pitch-1, are not written.
  *
  * Checked before the launch, in this order:

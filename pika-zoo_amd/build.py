@@ -15,8 +15,8 @@ a fifth, bound by pikazoo_amd/ppo.py, which shares csrc/pz_policy_rows.hpp with 
 (include/pikazoo_netgrad.h: pz_mlp_backward) a seventh, bound by pikazoo_amd/netgrad.py; the optimizer library
 (include/pikazoo_optim.h: pz_adam_step) an eighth, bound by pikazoo_amd/optim.py; the batch library
 (include/pikazoo_batch.h: pz_batch_copy, pz_batch_gather) a ninth, bound by pikazoo_amd/batch.py; the pool library
-(include/pikazoo_pool.h: pz_pool_plan, pz_mlp_forward_pool) a tenth, bound by pikazoo_amd/pool.py, whose tile code
-(csrc/pz_pool_tile.hpp) restates the sixth's.  The ten compiles are independent and run side by side.
+(include/pikazoo_pool.h: pz_pool_plan, pz_mlp_forward_pool) a tenth, bound by pikazoo_amd/pool.py, which shares its tile
+code (csrc/pz_mlp_tile.hpp) with the sixth.  The ten compiles are independent and run side by side.
 """
 from __future__ import annotations
 
@@ -52,9 +52,13 @@ NETGRAD_SOURCES = [CSRC / "pz_netgrad.hip"]
 OPTIM_SOURCES = [CSRC / "pz_optim.hip"]
 BATCH_SOURCES = [CSRC / "pz_batch.hip"]
 POOL_SOURCES = [CSRC / "pz_pool.hip"]
-DEPS = SOURCES + DIAG_SOURCES + LEARN_SOURCES + POLICY_SOURCES + PPO_SOURCES + NET_SOURCES + NETGRAD_SOURCES + OPTIM_SOURCES + BATCH_SOURCES + POOL_SOURCES + [
+# every library with the translation units it is compiled from
+TARGETS = ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES), (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES),
+           (NET_LIB, NET_SOURCES), (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES),
+           (POOL_LIB, POOL_SOURCES))
+DEPS = [source for _, sources in TARGETS for source in sources] + [
     CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
-    CSRC / "pz_policy_rows.hpp", CSRC / "pz_pool_tile.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
+    CSRC / "pz_policy_rows.hpp", CSRC / "pz_mlp_tile.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
     INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h",
     INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h"]
 ARCH = "gfx950"
@@ -99,8 +103,7 @@ def library_id(lib: Path = LIB):
 
 
 def needs_build() -> bool:
-    return any(library_id(lib) != source_id() for lib in (LIB, DIAG_LIB, LEARN_LIB, POLICY_LIB, PPO_LIB, NET_LIB, NETGRAD_LIB,
-                                                                 OPTIM_LIB, BATCH_LIB, POOL_LIB))
+    return any(library_id(lib) != source_id() for lib, _ in TARGETS)
 
 
 def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
@@ -124,11 +127,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
         raise ValueError("a diagnostic build (-DPZ_DIAGNOSTIC_BUILD) is never written to the product library's path")
     want = source_id(tuple(extra_flags))
     LIB_DIR.mkdir(parents=True, exist_ok=True)
-    todo = [(out, sources) for out, sources in ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES),
-                                                (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES), (NET_LIB, NET_SOURCES),
-                                                (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES),
-                                                (POOL_LIB, POOL_SOURCES))
-            if force or extra_flags or library_id(out) != want]
+    todo = [(out, sources) for out, sources in TARGETS if force or extra_flags or library_id(out) != want]
     if len(todo) > 1:
         from concurrent.futures import ThreadPoolExecutor
 

@@ -1,8 +1,7 @@
-// The tile of libpikazoo_pool.so: the staging of one parameter set into LDS in operand order and the three layers of one tile
-// of 32 batch rows.  It RESTATES the device code of pz_net.hip (libpikazoo_net.so) -- same k order, same operand permutation,
-// same roundings -- because include/pikazoo_pool.h promises pz_mlp_forward's bits for every row; the two must be kept in step,
-// and tests/test_gpu_pool.py compares them bit for bit.  (Sharing one header was tried first: it moved the instruction streams
-// of libpikazoo_net.so's kernels, so pz_net.hip stays as it is -- DESIGN.md 4.21.)
+// The policy net's forward tile, shared by libpikazoo_net.so (pz_net.hip) and libpikazoo_pool.so (pz_pool.hip): the staging of
+// one parameter set into LDS in operand order, the three layers of one tile of 32 batch rows, and what the two entry points
+// check and size alike.  include/pikazoo_pool.h promises pz_mlp_forward's bits for every row: both kernels call tile_forward,
+// so the k order, the operand permutation and the roundings are written down here and nowhere else.
 //
 // Every layer is computed as W . X^T on v_mfma_f32_32x32x2_f32 (exact float32: a k-ordered chain of fused multiply-adds):
 // the weights are the A operand, a tile of 32 batch rows the B operand, so an accumulator tile has its hidden index in the
@@ -22,7 +21,7 @@
 
 #include "pikazoo_net.h"
 
-namespace pz_pool {
+namespace pz_mlp {
 
 constexpr int kThreads = 256;  // four waves, one per SIMD, share one staged parameter set
 constexpr int kWaves = kThreads / 64;
@@ -276,4 +275,15 @@ static inline bool bad_pitch(int64_t n, int64_t width, int64_t pitch)
     return n > 0 && pitch > (INT64_MAX / 4) / n;  // n * pitch * 4 bytes: refused, never wrapped
 }
 
-}  // namespace pz_pool
+// The most workgroups a launch of `sides` agents asks for: two resident workgroups per CU where the LDS holds two parameter
+// sets (the loads of one hide under the other's products), else one, divided over the sides.
+static inline int64_t grid_cap(size_t lds_bytes, unsigned sides)
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    const int64_t resident = (int64_t)cus * (2 * lds_bytes <= (size_t)kLdsBytes ? 2 : 1);
+    return (resident + sides - 1) / sides;
+}
+
+}  // namespace pz_mlp

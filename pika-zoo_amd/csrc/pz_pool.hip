@@ -2,8 +2,8 @@
 // member, in ONE launch -- and the plan that groups the rows by member (C ABI and the definition: include/pikazoo_pool.h; the
 // shape and its reasons: DESIGN.md 4.21).
 //
-// The tile body is pz_pool_tile.hpp's, a restatement of the code pz_mlp_forward runs: same k order, same operand permutation,
-// same bits.  What is new here is which rows a tile holds and which parameter set is staged under it.  The plan's `order` lists the rows member
+// The tile body is pz_mlp_tile.hpp's, the code pz_mlp_forward runs: same k order, same operand permutation, same bits.  What
+// is new here is which rows a tile holds and which parameter set is staged under it.  The plan's `order` lists the rows member
 // by member in groups of G = 128 slots (pads are -1), so the four waves of a workgroup always share a member: a workgroup
 // takes a contiguous range of groups, finds a group's member by comparing its first slot with the P + 1 words of `first`
 // (held in LDS), and re-stages the parameters only when the member changes.
@@ -12,9 +12,11 @@
 
 #include "pikazoo_hip.h"
 #include "pikazoo_pool.h"
-#include "pz_pool_tile.hpp"
+#include "pz_mlp_tile.hpp"
 
 namespace pz_pool {
+
+using namespace pz_mlp;
 
 constexpr int G = PZ_POOL_GROUP_ROWS;
 constexpr int kMaxMembers = PZ_POOL_MAX_MEMBERS;
@@ -179,15 +181,9 @@ static int launch(const Args& a, unsigned sides, void* stream)
         const hipError_t e = hipFuncSetAttribute((const void*)mlp_forward_pool_kernel<H, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
         if (e != hipSuccess) return (int)e;
     }
-    // as pz_mlp_forward: two resident workgroups per CU where the LDS holds two parameter sets
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    const int64_t resident = (int64_t)cus * (2 * bytes <= (size_t)kLdsBytes ? 2 : 1);
     int64_t blocks = 1;
     for (unsigned side = 0; side < sides; ++side) blocks = max(blocks, (int64_t)(a.order[side] ? a.plan_groups : a.plain_groups));
-    const int64_t cap = (resident + sides - 1) / sides;
-    if (blocks > cap) blocks = cap;
+    blocks = min(blocks, grid_cap(bytes, sides));
     hipLaunchKernelGGL((mlp_forward_pool_kernel<H, ACT>), dim3((unsigned)blocks, sides), dim3(kThreads), bytes, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -122,31 +122,40 @@ def _pz_build():
     return mod
 
 
-def load():
-    """Load the shared library (once).  Raises if it has not been built, or if it was built from other
-    sources than the ones in this tree (the library is git-ignored but travels with the working tree,
-    so a stale one would otherwise be run silently)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
+def load_library(path, source_name, signatures, abi_symbol, abi_version, fallback_word="torch"):
+    """What every binding's ``load()`` does on its first call: `path` must exist; in a source tree (csrc/`source_name` is
+    there) it must carry the build id of these sources (the library is git-ignored but travels with the working tree, so a
+    stale one would otherwise be run silently); it is opened, every export of `signatures` ({name: (restype, argtypes)}) is
+    given its types, and `abi_symbol`() must return `abi_version`.  Returns the handle; raises otherwise."""
+    if not path.exists():
         raise PikazooNativeError(
-            f"{LIB_PATH} is missing: build it with `python pika-zoo_amd/build.py` "
-            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    if (PKG_ROOT / "csrc" / "pz_kernels.hip").exists():  # a source tree: the library must match it
+            f"{path} is missing: build it with `python pika-zoo_amd/build.py` (hipcc --offload-arch=gfx950). "
+            f"There is no {fallback_word} fallback.")
+    if (PKG_ROOT / "csrc" / source_name).exists():  # a source tree: the library must match it
         b = _pz_build()
-        have, want = b.library_id(LIB_PATH), b.source_id()
+        have, want = b.library_id(path), b.source_id()
         if have != want:
             raise PikazooNativeError(
-                f"{LIB_PATH} is stale: built from sources {have}, the tree holds {want}; rebuild it with "
+                f"{path} is stale: built from sources {have}, the tree holds {want}; rebuild it with "
                 "`python pika-zoo_amd/build.py`")
-    lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    lib = C.CDLL(str(path))
+    for name, (restype, argtypes) in signatures.items():
         fn = getattr(lib, name)  # AttributeError if the export is missing
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.pz_abi_version() != ABI_VERSION:
-        raise PikazooNativeError(f"ABI mismatch: library {lib.pz_abi_version()} != binding {ABI_VERSION}")
+    have = getattr(lib, abi_symbol)()
+    if have != abi_version:
+        raise PikazooNativeError(f"ABI mismatch: library {have} != binding {abi_version}")
+    return lib
+
+
+def load():
+    """Load the shared library (once).  Raises if it has not been built, or if it was built from other
+    sources than the ones in this tree."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    lib = load_library(LIB_PATH, "pz_kernels.hip", _SIGNATURES, "pz_abi_version", ABI_VERSION, fallback_word="CPU")
     if lib.pz_config_bytes() != C.sizeof(PzConfig) or lib.pz_state_words() != STATE_WORDS \
             or lib.pz_obs_dim() != OBS_DIM:
         raise PikazooNativeError("pz_config / state layout of the library does not match this binding")

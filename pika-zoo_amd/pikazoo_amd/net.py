@@ -48,28 +48,9 @@ def load():
     """Load libpikazoo_net.so (once).  Raises if it has not been built or was built from other sources than the ones in
     this tree."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise _native.PikazooNativeError(
-            f"{LIB_PATH} is missing: build it with `python pika-zoo_amd/build.py` (hipcc --offload-arch=gfx950). "
-            "There is no torch fallback.")
-    if (_native.PKG_ROOT / "csrc" / "pz_net.hip").exists():  # a source tree: the library must match it
-        b = _native._pz_build()
-        have, want = b.library_id(LIB_PATH), b.source_id()
-        if have != want:
-            raise _native.PikazooNativeError(
-                f"{LIB_PATH} is stale: built from sources {have}, the tree holds {want}; rebuild it with "
-                "`python pika-zoo_amd/build.py`")
-    lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the export is missing
-        fn.restype = restype
-        fn.argtypes = argtypes
-    if lib.pz_net_abi_version() != ABI_VERSION:
-        raise _native.PikazooNativeError(f"ABI mismatch: library {lib.pz_net_abi_version()} != binding {ABI_VERSION}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _native.load_library(LIB_PATH, "pz_net.hip", SIGNATURES, "pz_net_abi_version", ABI_VERSION)
+    return _lib
 
 
 def _sides(x, what):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import capture_net_bits as B
 import net_judge as N
 import policy_judge as J
 from test_gpu_policy import SENT, TAIL, cpu, stream
@@ -219,6 +220,24 @@ def test_bits_do_not_depend_on_the_batch(lib):
     assert np.array_equal(bits(swapped[1]), bits(whole[0])) and np.array_equal(bits(swapped[0]), bits(whole[1]))
     single = run_forward(lib, [obs[0][77:78]], "float32", [params[0]], "tanh")
     assert np.array_equal(bits(single[0]), bits(whole[0][77:78]))
+
+
+def test_bits_are_the_recorded_ones(lib):
+    """tests/golden/net_forward_bits.json (tests/capture_net_bits.py) holds digests of what pz_mlp_forward wrote, taken from
+    the library before its tile moved into csrc/pz_mlp_tile.hpp: every case must give those bits.  Every other test here
+    allows a tolerance, and the pool's comparisons hold the tile to itself.  No skip on another compiler: tanhf comes from the
+    toolchain, and a toolchain change is a reason to look."""
+    import json
+
+    record = json.loads(B.PATH.read_text())
+    have = B.digests(lib, run_forward, obs_bits)
+    assert list(have) == list(record["cases"]), "the cases are not the recorded ones"
+    inputs = [name for name in have if have[name]["inputs"] != record["cases"][name]["inputs"]]
+    moved = [name for name in have if have[name]["outputs"] != record["cases"][name]["outputs"]]
+    if inputs or moved:
+        print(f"recorded compiler: {record['compiler']}\ncurrent compiler:  {B.compiler_line()}")
+    assert not inputs, f"the INPUTS differ from the recorded ones (net_judge.make_obs / make_params changed?): {inputs}"
+    assert not moved, f"pz_mlp_forward no longer writes the recorded bits (recorded from build {record['build_id']}): {moved}"
 
 
 def test_zero_rows_launch_nothing(lib):

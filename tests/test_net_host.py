@@ -51,6 +51,7 @@ def test_net_library_exports_exactly_its_header(pz_build, net_lib):
     assert pz_build.library_id(pz_build.NET_LIB) == pz_build.source_id() == net_lib.pz_net_build_id().decode()
     assert not pz_build.needs_build()
     assert pz_build.NET_SOURCES[0] in pz_build.DEPS and (pz_build.INCLUDE / "pikazoo_net.h") in pz_build.DEPS
+    assert (pz_build.CSRC / "pz_mlp_tile.hpp") in pz_build.DEPS
     assert net_lib.pz_net_abi_version() == net.ABI_VERSION == 1
     header = (REPO / "include" / "pikazoo_net.h").read_text()
     assert "#define PZ_NET_ABI_VERSION 1" in header

@@ -150,7 +150,7 @@ def test_pool_library_exports_exactly_its_header(pz_build, lib):
     assert pz_build.library_id(pz_build.POOL_LIB) == pz_build.source_id() == lib.pz_pool_build_id().decode()
     assert not pz_build.needs_build()
     assert pz_build.POOL_SOURCES[0] in pz_build.DEPS and (pz_build.INCLUDE / "pikazoo_pool.h") in pz_build.DEPS
-    assert (pz_build.CSRC / "pz_pool_tile.hpp") in pz_build.DEPS
+    assert (pz_build.CSRC / "pz_mlp_tile.hpp") in pz_build.DEPS
     assert lib.pz_pool_abi_version() == pool.ABI_VERSION == 1
     header = (REPO / "include" / "pikazoo_pool.h").read_text()
     assert "#define PZ_POOL_ABI_VERSION 1" in header
