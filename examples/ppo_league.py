@@ -10,8 +10,14 @@ the draw is renewed once per iteration: ``pool.plan`` groups the games by member
 ``pool.Snapshots.act`` (ONE launch for both sides, each row through its own member's net) -> ``policy.sample`` -> ``env.step``.
 Every ``--snapshot-every`` iterations ``push()`` freezes the learner's parameters into the next slot of the ring.  The update
 uses ``player_1``'s samples only, through ``ActorCritic.evaluate`` -> ``ppo.loss`` -> ``backward`` -> ``optim.Adam.step``; the
-snapshots have no gradients.  How opponents are drawn (uniformly here) is plain torch in this loop: prioritised sampling or a
-rating would replace the ``randint``.
+snapshots have no gradients.
+
+``--pfsp`` turns the pool into a league (``pikazoo_amd.league``): a ``Matchmaker`` records every finished game against the
+member it was played against (``record`` after every ``env.step``, one launch), draws the opponents by prioritised fictitious
+self-play -- members the learner loses to more often -- once per iteration (``rematch()``: the weights, one draw launch, the
+plan), pushes the snapshots through it so that an overwritten slot does not inherit results, and the log shows the learner's
+win rate against each member.  Without the flag the opponents are drawn uniformly with ``torch.randint`` and nobody keeps
+score: the loop launches what it launched before the flag existed.
 """
 import argparse
 import sys
@@ -21,12 +27,13 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
+from pikazoo_amd import league as matchmaking  # noqa: E402
 from pikazoo_amd import learn, net, optim, pikazoo_v0, policy, pool, ppo  # noqa: E402
 from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print, pool_size=8,
-         snapshot_every=2):
+         snapshot_every=2, pfsp=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -37,6 +44,7 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
     model = net.ActorCritic(in_features=K, hidden=64, num_actions=A).to(device)
     optimizer = optim.Adam(model.parameters(), lr=lr, eps=1e-5, max_grad_norm=0.5)
     league = pool.Snapshots(model, pool_size)
+    matchmaker = matchmaking.Matchmaker(league, num_envs, seed=seed) if pfsp else None
 
     n, k = num_envs, steps
     buf_obs = torch.empty((k, n, K), dtype=obs[learner].dtype, device=device)
@@ -51,10 +59,13 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
 
     for it in range(iters):
         if it % snapshot_every == 0 and pool_size > 1:
-            league.push()
+            matchmaker.push() if pfsp else league.push()
         # ---- every game draws its opponent; the games are grouped by member once per iteration -------------------------------
-        members = torch.randint(len(league), (n,), device=device)
-        plan = plans[len(league)] = pool.plan(members, len(league), out=plans.get(len(league)))
+        if pfsp:
+            plan = matchmaker.rematch()                           # PFSP weights from the results so far, one draw, the plan
+        else:
+            members = torch.randint(len(league), (n,), device=device)
+            plan = plans[len(league)] = pool.plan(members, len(league), out=plans.get(len(league)))
         sides = {learner: None, opponent: plan}                   # the learner's side needs no plan: member 0 everywhere
 
         # ---- rollout: k policy steps, three launches each (net over the pool, head, step) ---------------------------------
@@ -66,6 +77,8 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
             buf_logp[t].copy_(picked["log_probs"][learner])
             buf_val[t].copy_(head[learner][:, A])
             obs, rewards, terminations, _, _ = env.step(picked["actions"])
+            if pfsp:
+                matchmaker.record(terminations[learner], env.scores)   # the terminal frame's scores: the reset comes with the next step
             buf_rew[t].copy_(rewards[learner])
             buf_term[t].copy_(terminations[learner])
             policy_step += 1
@@ -89,8 +102,13 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
                 loss[learner].backward()
                 optimizer.step()
                 losses.append(loss[learner].detach())
-        log(f"iter {it}: pool {len(league)} | loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][learner]):.3f} | "
-            f"approx_kl {float(stats['approx_kl'][learner]):.5f} | mean reward {float(buf_rew.mean()):+.5f}")
+        line = (f"iter {it}: pool {len(league)} | loss {float(losses[-1]):+.4f} | entropy {float(stats['entropy'][learner]):.3f} | "
+                f"approx_kl {float(stats['approx_kl'][learner]):.5f} | mean reward {float(buf_rew.mean()):+.5f}")
+        if pfsp:
+            matchmaker.check()
+            rates, games = matchmaker.win_rates().tolist(), matchmaker.table[0, :, 0].tolist()
+            line += " | win rate " + " ".join(f"{m}:{rates[m]:.2f}/{games[m]}" if games[m] else f"{m}:-" for m in range(len(league)))
+        log(line)
     return [float(x) for x in losses]
 
 
@@ -101,5 +119,6 @@ if __name__ == "__main__":
     p.add_argument("--steps", type=int, default=16)
     p.add_argument("--pool", type=int, default=8, help="pool members: the learner and pool - 1 snapshots (at most 16)")
     p.add_argument("--snapshot-every", type=int, default=2, help="iterations between two snapshots of the learner")
+    p.add_argument("--pfsp", action="store_true", help="a league: record results per member and draw opponents by prioritised fictitious self-play")
     args = p.parse_args()
-    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every)
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every, pfsp=args.pfsp)

@@ -26,16 +26,19 @@
 
     from pikazoo_amd import pool                       # the net's forward for a pool of snapshots: each row its own member's net
     head = pool.Snapshots(model, capacity=8).act(obs, {"player_1": None, "player_2": pool.plan(members, 8)})
+
+    from pikazoo_amd import league                     # league matchmaking: per-member results and weighted draws, one launch each
+    table = league.tally(terminations, env.scores, members, 8); members = league.draw(league.pfsp_weights(table, 8), n, seed=0)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
