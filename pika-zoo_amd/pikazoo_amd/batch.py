@@ -13,7 +13,7 @@ every tensor of a shuffled minibatch out of them in ONE launch, the permutation 
     batch.permutation(M, seed=0, epoch=e)             # int64[M]: the order gather visits the rows in
 
 ctypes binding of libpikazoo_batch.so (C ABI and the definition: include/pikazoo_batch.h), a library of its own beside the
-product library; nothing in the step path or in the other modules imports this one.  There is no torch fallback: a missing or
+product library; nothing in the step path or in the other modules imports this one, and it imports none of them.  There is no torch fallback: a missing or
 stale library raises.  A launch allocates nothing and does not synchronise: it can be captured in a graph, and a counter
 given as a device tensor is read at run time.  Every tensor is a COLUMN described by bytes, so any dtype and any agent is
 just another column; at most 16 columns per launch, rows of at most 512 bytes.
@@ -24,7 +24,7 @@ import ctypes as C
 
 import torch
 
-from . import _native, net
+from . import _launch, _native
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_batch.so"
 ABI_VERSION = 1
@@ -49,8 +49,8 @@ SIGNATURES = {
     # (cols, ncols, k, n, minibatches, seed, counter, counter_dev, index_in, index_out, errors, stream)
     "pz_batch_gather": (C.c_int, [C.POINTER(Column), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a count, a pitch or an extent beyond the kernel's range",
-           -3: "an element size other than 1, 2, 4 or 8", -4: "a pointer, pitch or row not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a count, a pitch or an extent beyond the kernel's range", -3: "an element size other than 1, 2, 4 or 8",
+           -4: "a pointer, pitch or row not aligned to its element"}
 _lib = None
 
 
@@ -128,15 +128,6 @@ def _need_gpu(dev):
         raise ValueError(f"the batch launches run on the GPU: the tensors are on {dev}")
 
 
-def _stream(index):
-    return net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-
-
-def _check(code, name):
-    if code != 0:
-        raise _native.PikazooNativeError(f"{name} failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
-
-
 # ---- copy ----------------------------------------------------------------------------------------------------------------------
 def _plan_copy(pairs):
     """Every check that needs no library, then (Column array, ncols, n, device).  The structs hold addresses only."""
@@ -163,19 +154,14 @@ def _plan_copy(pairs):
     if n > MAX_ROWS:
         raise ValueError(f"at most 2^31 rows, got {n}")
     dev = _device([t for pair in pairs for t in pair])
-    net._no_alias([(f"pairs[{i}] dst", d) for i, (_, d) in enumerate(pairs)], [(f"pairs[{i}] src", s) for i, (s, _) in enumerate(pairs)])
+    _launch.no_alias([(f"pairs[{i}] dst", d) for i, (_, d) in enumerate(pairs)], [(f"pairs[{i}] src", s) for i, (s, _) in enumerate(pairs)])
     _need_gpu(dev)
     return array, len(pairs), n, dev
 
 
 def _launch_copy(array, ncols, n, dev):
-    if n == 0:
-        return
-    lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_batch_copy(array, ncols, n, _stream(index))
-    _check(code, "pz_batch_copy")
+    if n:
+        _launch.launch(load().pz_batch_copy, _ERRORS, dev, array, ncols, n)
 
 
 def copy(pairs):
@@ -192,8 +178,7 @@ def copy(pairs):
 # ---- gather --------------------------------------------------------------------------------------------------------------------
 def _int_word(t, what, dev):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != 1 or t.device != dev:
-        raise ValueError(f"{what} must be one int64 element on {dev}, got "
-                         f"{type(t).__name__ if not isinstance(t, torch.Tensor) else f'{t.dtype} {list(t.shape)} on {t.device}'}")
+        raise ValueError(f"{what} must be one int64 element on {dev}, got {_launch.describe(t)}")
     return t
 
 
@@ -268,19 +253,15 @@ class _GatherPlan:
         dev = _device([t for _, t in leaves] + outs + [t for _, t in extras])
         outputs = [(_name("out", p), o) for (p, _), o in zip(leaves, outs)] + [(name, t) for name, t in extras if name in ("index_out", "errors")]
         inputs = [(_name("sources", p), t) for p, t in leaves] + [(name, t) for name, t in extras if name in ("counter_dev", "index")]
-        net._no_alias(outputs, inputs)
+        _launch.no_alias(outputs, inputs)
         _need_gpu(dev)
         self.array, self.ncols, self.dev = array, len(leaves), dev
-        self.index = dev.index if dev.index is not None else torch.cuda.current_device()
         self.pointers = tuple(t.data_ptr() if t is not None else None for t in (counter_dev, index, index_out, errors))
         self._alive = (leaves, outs, extras)
 
     def launch(self, counter=None):
-        lib = load()
-        with torch.cuda.device(self.index):
-            code = lib.pz_batch_gather(self.array, self.ncols, self.k, self.n, self.passed, self.seed, self.counter if counter is None else counter,
-                                       *self.pointers, _stream(self.index))
-        _check(code, "pz_batch_gather")
+        _launch.launch(load().pz_batch_gather, _ERRORS, self.dev, self.array, self.ncols, self.k, self.n, self.passed, self.seed,
+                       self.counter if counter is None else counter, *self.pointers)
         return self.result
 
 
@@ -311,10 +292,7 @@ def permutation(M, seed, epoch, device=None):
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     _need_gpu(dev)
     out = torch.empty(M, dtype=torch.int64, device=dev)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = load().pz_batch_gather(None, 0, 1, M, 1, seed & 0xFFFFFFFFFFFFFFFF, epoch, None, None, out.data_ptr(), None, _stream(index))
-    _check(code, "pz_batch_gather")
+    _launch.launch(load().pz_batch_gather, _ERRORS, dev, None, 0, 1, M, 1, seed & 0xFFFFFFFFFFFFFFFF, epoch, None, None, out.data_ptr(), None)
     return out
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._launch import raw_stream as _raw_stream
 from .spaces import Box, Discrete
 
 # The reference is `class raw_env(ParallelEnv)` (pikazoo_env.py:72) and downstream libraries test `isinstance(env,
@@ -78,16 +79,9 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 
-# torch.cuda.current_stream(...).cuda_stream builds a Stream object per call (2.8 us); the raw getter behind it
-# costs 0.08 us, which keeps env.step()'s host side (about 5.5 us) below the duration of the launch it issues
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+# (_raw_stream: the raw getter costs 0.08 us instead of 2.8, which keeps env.step()'s host side (about 5.5 us) below the
+# duration of the launch it issues)
 _get_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device  # (the raw getter: 0.1 us instead of 0.3)
-
-
-def _raw_stream(device_index: int) -> int:
-    if _get_raw_stream is not None:
-        return _get_raw_stream(device_index)
-    return torch.cuda.current_stream(device_index).cuda_stream
 
 
 # The computer player's flight look-up tables (pz_flight_tables in include/pikazoo_hip.h): caller-owned

@@ -15,7 +15,8 @@ ONE launch, and a member per game drawn with integer weights from a counter in O
     weights = league.pfsp_weights(table, active=P)               # prioritised fictitious self-play, or any int64 [P] of yours
 
 ctypes binding of libpikazoo_league.so (C ABI and the definitions: include/pikazoo_league.h), a library of its own beside the
-product library; nothing in the step path or in the other modules imports this one, and importing it loads nothing.  There
+product library; nothing in the step path or in the other modules imports this one, and importing it loads nothing and imports
+none of them (``Matchmaker`` imports ``pool`` when it is made).  There
 is no torch fallback: a missing or stale library raises.  Both launches are integer arithmetic, fixed bit for bit by the
 header; they allocate nothing and do not synchronise, so they can be captured in a graph, and a counter given as a device
 tensor is read at run time.
@@ -26,7 +27,8 @@ import ctypes as C
 
 import torch
 
-from . import _native, net
+from . import _launch, _native
+from ._launch import describe as _describe
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_league.so"
 ABI_VERSION = 1
@@ -49,8 +51,7 @@ SIGNATURES = {
     # (weights, num_members, seed, counter, counter_dev, first_game, mask, members, member_format, n, errors, stream)
     "pz_league_draw": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_uint64, _P, C.c_int64, _P, _P, C.c_int32, C.c_int64, _P, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a count, a stride or a counter beyond the kernel's range",
-           -3: "an unknown score or member format", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a count, a stride or a counter beyond the kernel's range", -3: "an unknown score or member format"}
 _lib = None
 
 
@@ -61,19 +62,6 @@ def load():
     if _lib is None:
         _lib = _native.load_library(LIB_PATH, "pz_league.hip", SIGNATURES, "pz_league_abi_version", ABI_VERSION)
     return _lib
-
-
-def _stream(index):
-    return net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-
-
-def _check(code, name):
-    if code != 0:
-        raise _native.PikazooNativeError(f"{name} failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
-
-
-def _describe(t):
-    return f"{t.dtype} {list(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
 
 
 def _is_int(x):
@@ -157,7 +145,7 @@ def tally(terminations, scores, members, num_members, table=None, members_p1=Non
     dev = _one_device(given)
     outputs = [(name, t) for name, t in (("table", table), ("errors", errors)) if t is not None]
     if outputs:
-        net._no_alias(outputs, [(name, t) for name, t in given if name not in ("table", "errors")])
+        _launch.no_alias(outputs, [(name, t) for name, t in given if name not in ("table", "errors")])
     _need_gpu(dev)
     if table is None:
         table = torch.zeros((P, P, CELL_WORDS), dtype=torch.int64, device=dev)
@@ -165,14 +153,10 @@ def tally(terminations, scores, members, num_members, table=None, members_p1=Non
         errors = torch.zeros(1, dtype=torch.int64, device=dev)
     if n == 0:
         return table
-    lib = load()
-    elem = scores.element_size()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_league_tally(terminations.data_ptr(), scores.data_ptr(), scores.data_ptr() + int(scores.stride(1)) * elem,
-                                   SCORE_FORMATS[scores.dtype], stride, members_p1.data_ptr() if members_p1 is not None else None,
-                                   members.data_ptr(), MEMBER_FORMATS[members.dtype], n, P, table.data_ptr(), errors.data_ptr(), _stream(index))
-    _check(code, "pz_league_tally")
+    _launch.launch(load().pz_league_tally, _ERRORS, dev, terminations.data_ptr(), scores.data_ptr(),
+                   scores.data_ptr() + int(scores.stride(1)) * scores.element_size(), SCORE_FORMATS[scores.dtype], stride,
+                   members_p1.data_ptr() if members_p1 is not None else None, members.data_ptr(), MEMBER_FORMATS[members.dtype], n, P,
+                   table.data_ptr(), errors.data_ptr())
     return table
 
 
@@ -223,7 +207,7 @@ def draw(weights, n, seed, counter=0, first_game=0, mask=None, out=None, dtype=t
     dev = _one_device(given)
     outputs = [(name, t) for name, t in (("out", out), ("errors", errors)) if t is not None]
     if outputs:
-        net._no_alias(outputs, [(name, t) for name, t in given if name not in ("out", "errors")])
+        _launch.no_alias(outputs, [(name, t) for name, t in given if name not in ("out", "errors")])
     _need_gpu(dev)
     if out is None:
         out = (torch.zeros if mask is not None else torch.empty)(n, dtype=dtype, device=dev)
@@ -231,13 +215,9 @@ def draw(weights, n, seed, counter=0, first_game=0, mask=None, out=None, dtype=t
         errors = torch.zeros(1, dtype=torch.int32, device=dev)
     if n == 0:
         return out
-    lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_league_draw(weights.data_ptr(), P, seed & 0xFFFFFFFFFFFFFFFF, counter, counter_dev.data_ptr() if counter_dev is not None else None,
-                                  first_game, mask.data_ptr() if mask is not None else None, out.data_ptr(), MEMBER_FORMATS[out.dtype], n,
-                                  errors.data_ptr(), _stream(index))
-    _check(code, "pz_league_draw")
+    _launch.launch(load().pz_league_draw, _ERRORS, dev, weights.data_ptr(), P, seed & 0xFFFFFFFFFFFFFFFF, counter,
+                   counter_dev.data_ptr() if counter_dev is not None else None, first_game, mask.data_ptr() if mask is not None else None,
+                   out.data_ptr(), MEMBER_FORMATS[out.dtype], n, errors.data_ptr())
     return out
 
 

@@ -17,7 +17,7 @@ from typing import Optional
 
 import torch
 
-from . import _native
+from . import _launch, _native
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_learn.so"
 ABI_VERSION = 1
@@ -33,10 +33,9 @@ SIGNATURES = {
     "pz_gae": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                          C.c_int64, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size, a pitch or a tensor too large for the kernel's addressing",
-           -3: "an unknown format, or gamma / lam outside [0, 1]", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size, a pitch or a tensor too large for the kernel's addressing",
+           -3: "an unknown format, or gamma / lam outside [0, 1]"}
 _lib = None
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def load():
@@ -46,20 +45,6 @@ def load():
     if _lib is None:
         _lib = _native.load_library(LIB_PATH, "pz_learn.hip", SIGNATURES, "pz_learn_abi_version", ABI_VERSION)
     return _lib
-
-
-def _sides(x, what):
-    """(keys or None, [tensor, ...]) of a tensor or an {agent: tensor} dict of one or two agents"""
-    if isinstance(x, dict):
-        if not 1 <= len(x) <= 2:
-            raise ValueError(f"{what}: a dict of one or two agents, got {len(x)}")
-        keys, vals = list(x), list(x.values())
-    else:
-        keys, vals = None, [x]
-    for v in vals:
-        if not isinstance(v, torch.Tensor):
-            raise ValueError(f"{what} must be a tensor or a dict of tensors, got {type(v).__name__}")
-    return keys, vals
 
 
 def _pitch(ts, rows, n, what):
@@ -89,8 +74,8 @@ def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, o
     crosses an episode end.  The launch goes to the caller's current stream without a synchronisation, and without an
     allocation when ``out`` is the previous result of the same shapes: it can be captured into a graph.  Shape, dtype,
     device and range errors raise ``ValueError`` before any launch.  The outputs must not alias the inputs."""
-    keys, rew = _sides(rewards, "rewards")
-    vkeys, val = _sides(values, "values")
+    keys, rew = _launch.sides(rewards, "rewards")
+    vkeys, val = _launch.sides(values, "values")
     if vkeys != keys:
         raise ValueError(f"rewards and values must name the same agents in the same order: {keys} and {vkeys}")
     if isinstance(terminations, dict):
@@ -131,8 +116,8 @@ def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, o
     adv = ret = None
     if out is not None:
         a, r = out.get("advantages"), out.get("returns")
-        akeys, adv = _sides(a, "out['advantages']")
-        rkeys, ret = _sides(r, "out['returns']")
+        akeys, adv = _launch.sides(a, "out['advantages']")
+        rkeys, ret = _launch.sides(r, "out['returns']")
         if akeys != keys or rkeys != keys:
             raise ValueError(f"out= holds the agents {akeys} / {rkeys}, the call {keys}")
         for t in adv + ret:
@@ -143,19 +128,10 @@ def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, o
         adv = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
         ret = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
         out_pitch = n
-        out = {"advantages": dict(zip(keys, adv)) if keys is not None else adv[0],
-               "returns": dict(zip(keys, ret)) if keys is not None else ret[0]}
+        out = {"advantages": _launch.shape(keys, adv), "returns": _launch.shape(keys, ret)}
     if n == 0:
         return out
-    lib = load()
-    two = len(rew) == 2
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        stream = _get_raw_stream(index) if _get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-        code = lib.pz_gae(rew[0].data_ptr(), rew[1].data_ptr() if two else None, REWARD_FORMATS[r0.dtype], term.data_ptr(),
-                          val[0].data_ptr(), val[1].data_ptr() if two else None, VALUE_FORMATS[val[0].dtype], k, n,
-                          rew_pitch, term_pitch, val_pitch, out_pitch, gamma, lam, adv[0].data_ptr(),
-                          adv[1].data_ptr() if two else None, ret[0].data_ptr(), ret[1].data_ptr() if two else None, stream)
-    if code != 0:
-        raise _native.PikazooNativeError(f"pz_gae failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+    ptrs = _launch.ptrs
+    _launch.launch(load().pz_gae, _ERRORS, dev, *ptrs(rew), REWARD_FORMATS[r0.dtype], term.data_ptr(), *ptrs(val), VALUE_FORMATS[val[0].dtype],
+                   k, n, rew_pitch, term_pitch, val_pitch, out_pitch, gamma, lam, *ptrs(adv), *ptrs(ret))
     return out

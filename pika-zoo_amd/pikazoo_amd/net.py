@@ -10,7 +10,9 @@
 ctypes binding of libpikazoo_net.so (C ABI and the definition: include/pikazoo_net.h), a library of its own beside the
 product library; nothing in the step path, ``learn``, ``policy`` or ``ppo`` imports this module.  There is no torch
 fallback: a missing or stale library raises.  Operands and accumulation are float32, the parameters are torch's own
-``nn.Linear`` tensors read in place, and a row's bits do not depend on the batch around it.
+``nn.Linear`` tensors read in place, and a row's bits do not depend on the batch around it.  The argument check of the net
+(``_observations``, ``_box``, ``_outputs``) is also ``pool.forward``'s and ``netgrad.backward``'s; the launch plumbing is
+``_launch``'s.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ from typing import Optional
 
 import torch
 
-from . import _native
+from . import _launch, _native
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_net.so"
 ABI_VERSION = 1
@@ -38,10 +40,9 @@ SIGNATURES = {
     "pz_mlp_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size or a pitch beyond the kernel's range",
-           -3: "an unknown format or activation", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size or a pitch beyond the kernel's range", -3: "an unknown format or activation"}
+NAMES = ("W1", "b1", "W2", "b2", "W3", "b3")
 _lib = None
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def load():
@@ -51,41 +52,6 @@ def load():
     if _lib is None:
         _lib = _native.load_library(LIB_PATH, "pz_net.hip", SIGNATURES, "pz_net_abi_version", ABI_VERSION)
     return _lib
-
-
-def _sides(x, what):
-    """(keys or None, [tensor, ...]) of a tensor or an {agent: tensor} dict of one or two agents"""
-    if isinstance(x, dict):
-        if not 1 <= len(x) <= 2:
-            raise ValueError(f"{what}: a dict of one or two agents, got {len(x)}")
-        keys, vals = list(x), list(x.values())
-    else:
-        keys, vals = None, [x]
-    for v in vals:
-        if not isinstance(v, torch.Tensor):
-            raise ValueError(f"{what} must be a tensor or a dict of tensors, got {type(v).__name__}")
-    return keys, vals
-
-
-def _shape(keys, ts):
-    return dict(zip(keys, ts)) if keys is not None else ts[0]
-
-
-def _span(t):
-    """[first byte, last byte + 1) of the memory a tensor's elements lie in"""
-    if t.numel() == 0:
-        return t.data_ptr(), t.data_ptr()
-    return t.data_ptr(), t.data_ptr() + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
-
-
-def _no_alias(outputs, inputs):
-    """``ppo._no_alias``: no output overlaps an input or an earlier output"""
-    spans = [(what, _span(t)) for what, t in inputs]
-    for i, (what, t) in enumerate(outputs):
-        lo, hi = _span(t)
-        for other, (olo, ohi) in spans + [(w, _span(u)) for w, u in outputs[:i]]:
-            if lo < ohi and olo < hi:
-                raise ValueError(f"{what} overlaps {other}: outputs must not alias an input or each other")
 
 
 def _rows(ts, what, n, width, dtypes, dev):
@@ -123,6 +89,64 @@ def _parameter_sets(params, keys, sides):
     return out
 
 
+# ---- the argument check of every launch on this net: forward, pool.forward and netgrad.backward ---------------------------------
+def _observations(obs, activation):
+    """(keys, tensors, n, K, device, row pitch) of the observations of one or two agents, and the activation's name checked"""
+    keys, xs = _launch.sides(obs, "obs")
+    x0 = xs[0]
+    if x0.dim() != 2:
+        raise ValueError(f"obs must have shape [N, K], got {tuple(x0.shape)}")
+    n, K, dev = int(x0.shape[0]), int(x0.shape[1]), x0.device
+    if not 1 <= K <= MAX_IN:
+        raise ValueError(f"obs: 1 <= K <= {MAX_IN} features, got {K}")
+    if n > 1 << 30:
+        raise ValueError(f"obs: at most 2^30 rows, got {n}")
+    if x0.dtype not in OBS_FORMATS:
+        raise ValueError(f"obs must be {' or '.join(str(d) for d in OBS_FORMATS)}, got {x0.dtype}")
+    obs_pitch = _rows(xs, "obs", n, K, tuple(OBS_FORMATS), dev)
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be {' or '.join(repr(a) for a in ACTIVATIONS)}, got {activation!r}")
+    return keys, xs, n, K, dev, obs_pitch
+
+
+def _box(sets, K, dev, label=""):
+    """(H, O, the six shapes) of parsed parameter sets that all hold one net of the box for K features on `dev`; set ``m`` is
+    named ``label.format(m)`` in front of its tensor's name"""
+    w1 = sets[0][0]
+    if w1.dim() != 2:
+        raise ValueError(f"W1 must have shape [hidden, {K}], got {tuple(w1.shape)}")
+    H = int(w1.shape[0])
+    if H not in HIDDEN:
+        raise ValueError(f"hidden must be one of {HIDDEN}, got {H}")
+    w3 = sets[0][4]
+    if w3.dim() != 2:
+        raise ValueError(f"W3 must have shape [out_features, {H}], got {tuple(w3.shape)}")
+    O = int(w3.shape[0])
+    if not 1 <= O <= MAX_OUT:
+        raise ValueError(f"1 <= out_features <= {MAX_OUT}, got {O}")
+    shapes = ((H, K), (H,), (H, H), (H,), (O, H), (O,))
+    for m, ps in enumerate(sets):
+        for name, shape, p in zip(NAMES, shapes, ps):
+            if tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise ValueError(f"{label.format(m)}{name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {p.dtype} "
+                                 f"{list(p.shape)} on {p.device}{'' if p.is_contiguous() else ', not contiguous'}")
+    return H, O, shapes
+
+
+def _outputs(out, out_dtype, keys, n, O, dev):
+    """(the tensors of ``out=`` or None, their row pitch) of a forward; without ``out=``, ``out_dtype`` is checked instead"""
+    if out is None:
+        if out_dtype not in OUT_FORMATS:
+            raise ValueError(f"out_dtype must be {' or '.join(str(d) for d in OUT_FORMATS)}, got {out_dtype}")
+        return None, O
+    okeys, ys = _launch.sides(out, "out")
+    if okeys != keys:
+        raise ValueError(f"out must name the agents of obs in their order: {keys}, got {okeys}")
+    if ys[0].dtype not in OUT_FORMATS:
+        raise ValueError(f"out must be {' or '.join(str(d) for d in OUT_FORMATS)}, got {ys[0].dtype}")
+    return ys, _rows(ys, "out", n, O, tuple(OUT_FORMATS), dev)
+
+
 def forward(obs, params, activation: str = "tanh", out=None, out_dtype=torch.float32):
     """``W3 · act(W2 · act(W1 · x + b1) + b2) + b3`` for every observation row of one or both agents, in one launch
     (``pz_mlp_forward``).
@@ -139,71 +163,22 @@ def forward(obs, params, activation: str = "tanh", out=None, out_dtype=torch.flo
     (or ``[N, O]`` tensors at any common row stride) makes the call allocation-free; an output must not overlap an input
     or the other output.  The launch goes to the current stream without a synchronisation.  Shape, dtype, device and
     range errors raise ``ValueError`` before any launch."""
-    keys, xs = _sides(obs, "obs")
-    x0 = xs[0]
-    if x0.dim() != 2:
-        raise ValueError(f"obs must have shape [N, K], got {tuple(x0.shape)}")
-    n, K, dev = int(x0.shape[0]), int(x0.shape[1]), x0.device
-    if not 1 <= K <= MAX_IN:
-        raise ValueError(f"obs: 1 <= K <= {MAX_IN} features, got {K}")
-    if n > 1 << 30:
-        raise ValueError(f"obs: at most 2^30 rows, got {n}")
-    if x0.dtype not in OBS_FORMATS:
-        raise ValueError(f"obs must be {' or '.join(str(d) for d in OBS_FORMATS)}, got {x0.dtype}")
-    obs_pitch = _rows(xs, "obs", n, K, tuple(OBS_FORMATS), dev)
-    if activation not in ACTIVATIONS:
-        raise ValueError(f"activation must be {' or '.join(repr(a) for a in ACTIVATIONS)}, got {activation!r}")
+    keys, xs, n, K, dev, obs_pitch = _observations(obs, activation)
     sets = _parameter_sets(params, keys, len(xs))
-    w1 = sets[0][0]
-    if w1.dim() != 2:
-        raise ValueError(f"W1 must have shape [hidden, {K}], got {tuple(w1.shape)}")
-    H = int(w1.shape[0])
-    if H not in HIDDEN:
-        raise ValueError(f"hidden must be one of {HIDDEN}, got {H}")
-    w3 = sets[0][4]
-    if w3.dim() != 2:
-        raise ValueError(f"W3 must have shape [out_features, {H}], got {tuple(w3.shape)}")
-    O = int(w3.shape[0])
-    if not 1 <= O <= MAX_OUT:
-        raise ValueError(f"1 <= out_features <= {MAX_OUT}, got {O}")
-    names = ("W1", "b1", "W2", "b2", "W3", "b3")
-    shapes = ((H, K), (H,), (H, H), (H,), (O, H), (O,))
-    for ps in sets:
-        for name, shape, p in zip(names, shapes, ps):
-            if tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {p.dtype} {list(p.shape)} on "
-                                 f"{p.device}{'' if p.is_contiguous() else ', not contiguous'}")
-    if out is not None:
-        okeys, ys = _sides(out, "out")
-        if okeys != keys:
-            raise ValueError(f"out must name the agents of obs in their order: {keys}, got {okeys}")
-        if ys[0].dtype not in OUT_FORMATS:
-            raise ValueError(f"out must be {' or '.join(str(d) for d in OUT_FORMATS)}, got {ys[0].dtype}")
-        out_pitch = _rows(ys, "out", n, O, tuple(OUT_FORMATS), dev)
-    else:
-        if out_dtype not in OUT_FORMATS:
-            raise ValueError(f"out_dtype must be {' or '.join(str(d) for d in OUT_FORMATS)}, got {out_dtype}")
-        ys = None
-        out_pitch = O
+    H, O, _ = _box(sets, K, dev)
+    ys, out_pitch = _outputs(out, out_dtype, keys, n, O, dev)
     if dev.type != "cuda":
         raise ValueError(f"the policy net runs on the GPU: obs are on {dev}")
     if ys is None:
         ys = [torch.empty((n, O), dtype=out_dtype, device=dev) for _ in xs]
-        out = _shape(keys, ys)
-    _no_alias([(f"out[{s}]", y) for s, y in enumerate(ys)],
-              [(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"{name}[{s}]", p) for s, ps in enumerate(sets) for name, p in zip(names, ps)])
+        out = _launch.shape(keys, ys)
+    _launch.no_alias([(f"out[{s}]", y) for s, y in enumerate(ys)],
+                     [(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"{name}[{s}]", p) for s, ps in enumerate(sets) for name, p in zip(NAMES, ps)])
     if n == 0:
         return out
-    lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
     second = [p.data_ptr() for p in sets[1]] if len(xs) == 2 else [None] * 6
-    with torch.cuda.device(index):
-        stream = _get_raw_stream(index) if _get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-        code = lib.pz_mlp_forward(xs[0].data_ptr(), xs[1].data_ptr() if len(xs) == 2 else None, OBS_FORMATS[x0.dtype], n, K, obs_pitch,
-                                  H, O, ACTIVATIONS[activation], *[p.data_ptr() for p in sets[0]], *second, ys[0].data_ptr(),
-                                  ys[1].data_ptr() if len(xs) == 2 else None, OUT_FORMATS[ys[0].dtype], out_pitch, stream)
-    if code != 0:
-        raise _native.PikazooNativeError(f"pz_mlp_forward failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+    _launch.launch(load().pz_mlp_forward, _ERRORS, dev, *_launch.ptrs(xs), OBS_FORMATS[xs[0].dtype], n, K, obs_pitch, H, O, ACTIVATIONS[activation],
+                   *[p.data_ptr() for p in sets[0]], *second, *_launch.ptrs(ys), OUT_FORMATS[ys[0].dtype], out_pitch)
     return out
 
 

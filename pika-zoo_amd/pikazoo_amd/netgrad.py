@@ -13,7 +13,7 @@ ctypes binding of libpikazoo_netgrad.so (C ABI and the definition: include/pikaz
 product library; nothing in the step path, ``learn``, ``policy``, ``ppo`` or ``net`` imports this module.  There is no torch
 fallback: a missing or stale library raises.  Operands and accumulation are float32; the sums over the rows are
 deterministic (no atomics): two calls on the same inputs return the same bits.  Hidden widths 32, 64 and 128: the whole box
-of ``net.forward``.
+of ``net.forward``, checked by ``net``'s own argument check; the launch plumbing is ``_launch``'s.
 """
 from __future__ import annotations
 
@@ -21,12 +21,12 @@ import ctypes as C
 
 import torch
 
-from . import _native, net
+from . import _launch, _native, net
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_netgrad.so"
 ABI_VERSION = 1
 GRAD_FORMATS = net.OUT_FORMATS
-NAMES = ("W1", "b1", "W2", "b2", "W3", "b3")
+NAMES = net.NAMES
 
 _P = C.c_void_p
 SIGNATURES = {
@@ -39,8 +39,8 @@ SIGNATURES = {
     "pz_mlp_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [_P] * 12
                         + [_P, _P, C.c_int32, C.c_int64] + [_P] * 12 + [_P, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size or a pitch beyond the kernel's range",
-           -3: "an unknown format or activation, or a shared net on two parameter sets", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size or a pitch beyond the kernel's range",
+           -3: "an unknown format or activation, or a shared net on two parameter sets"}
 _lib = None
 
 
@@ -102,40 +102,10 @@ def backward(obs, params, grad_head, activation: str = "tanh", out=None, workspa
     overwritten, not accumulated into, and must not overlap an input, the workspace or each other.  The launches go to the
     current stream without a synchronisation.  Shape, dtype, stride, alias and range errors raise ``ValueError`` before the
     library is needed."""
-    keys, xs = net._sides(obs, "obs")
-    x0 = xs[0]
-    if x0.dim() != 2:
-        raise ValueError(f"obs must have shape [N, K], got {tuple(x0.shape)}")
-    n, K, dev = int(x0.shape[0]), int(x0.shape[1]), x0.device
-    if not 1 <= K <= net.MAX_IN:
-        raise ValueError(f"obs: 1 <= K <= {net.MAX_IN} features, got {K}")
-    if n > 1 << 30:
-        raise ValueError(f"obs: at most 2^30 rows, got {n}")
-    if x0.dtype not in net.OBS_FORMATS:
-        raise ValueError(f"obs must be {' or '.join(str(d) for d in net.OBS_FORMATS)}, got {x0.dtype}")
-    obs_pitch = net._rows(xs, "obs", n, K, tuple(net.OBS_FORMATS), dev)
-    if activation not in net.ACTIVATIONS:
-        raise ValueError(f"activation must be {' or '.join(repr(a) for a in net.ACTIVATIONS)}, got {activation!r}")
+    keys, xs, n, K, dev, obs_pitch = net._observations(obs, activation)
     sets = net._parameter_sets(params, keys, len(xs))
-    w1 = sets[0][0]
-    if w1.dim() != 2:
-        raise ValueError(f"W1 must have shape [hidden, {K}], got {tuple(w1.shape)}")
-    H = int(w1.shape[0])
-    if H not in net.HIDDEN:
-        raise ValueError(f"hidden must be one of {net.HIDDEN}, got {H}")
-    w3 = sets[0][4]
-    if w3.dim() != 2:
-        raise ValueError(f"W3 must have shape [out_features, {H}], got {tuple(w3.shape)}")
-    O = int(w3.shape[0])
-    if not 1 <= O <= net.MAX_OUT:
-        raise ValueError(f"1 <= out_features <= {net.MAX_OUT}, got {O}")
-    shapes = ((H, K), (H,), (H, H), (H,), (O, H), (O,))
-    for ps in sets:
-        for name, shape, p in zip(NAMES, shapes, ps):
-            if tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {p.dtype} {list(p.shape)} on "
-                                 f"{p.device}{'' if p.is_contiguous() else ', not contiguous'}")
-    gkeys, gs = net._sides(grad_head, "grad_head")
+    H, O, shapes = net._box(sets, K, dev)
+    gkeys, gs = _launch.sides(grad_head, "grad_head")
     if gkeys != keys:
         raise ValueError(f"grad_head must name the agents of obs in their order: {keys}, got {gkeys}")
     if gs[0].dtype not in GRAD_FORMATS:
@@ -164,10 +134,7 @@ def backward(obs, params, grad_head, activation: str = "tanh", out=None, workspa
                                      f"{list(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
     need = workspace_bytes(n, K, H, O, dev)
     if workspace is not None:
-        ws = workspace
-        if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous() or ws.device != dev
-                or ws.numel() < need or ws.data_ptr() % 16):
-            raise ValueError(f"the workspace must be a contiguous uint8 tensor of at least {need} bytes on {dev}, aligned to 16")
+        ws = _launch.check_workspace(workspace, need, dev)
     if dev.type != "cuda":
         raise ValueError(f"the policy net runs on the GPU: obs are on {dev}")
     if out is None:
@@ -176,7 +143,7 @@ def backward(obs, params, grad_head, activation: str = "tanh", out=None, workspa
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     inputs = ([(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"grad_head[{s}]", g) for s, g in enumerate(gs)]
               + [(f"{name}[{s}]", p) for s, ps in enumerate(sets) for name, p in zip(NAMES, ps)])
-    net._no_alias([(f"out[{s}].d{name}", t) for s, os_ in enumerate(outs) for name, t in zip(NAMES, os_)] + [("workspace", ws)], inputs)
+    _launch.no_alias([(f"out[{s}].d{name}", t) for s, os_ in enumerate(outs) for name, t in zip(NAMES, os_)] + [("workspace", ws)], inputs)
     if groups == 1 and (keys is None or shared):
         result = tuple(outs[0])
     else:
@@ -187,19 +154,17 @@ def backward(obs, params, grad_head, activation: str = "tanh", out=None, workspa
                 t.zero_()
         return result
     lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    index = _launch.device_index(dev)
     two = len(xs) == 2
     with torch.cuda.device(index):
         if lib.pz_mlp_backward_workspace_bytes(n, K, H, O) > ws.numel():
             raise _native.PikazooNativeError("the workspace is smaller than pz_mlp_backward_workspace_bytes asks for")
-        stream = net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
         code = lib.pz_mlp_backward(
-            xs[0].data_ptr(), xs[1].data_ptr() if two else None, net.OBS_FORMATS[x0.dtype], n, K, obs_pitch, H, O,
-            net.ACTIVATIONS[activation], *[p.data_ptr() for p in sets[0]], *([p.data_ptr() for p in sets[1]] if two else [None] * 6),
-            gs[0].data_ptr(), gs[1].data_ptr() if two else None, GRAD_FORMATS[gs[0].dtype], grad_pitch,
-            *[t.data_ptr() for t in outs[0]], *([t.data_ptr() for t in outs[1]] if groups == 2 else [None] * 6), ws.data_ptr(), stream)
-    if code != 0:
-        raise _native.PikazooNativeError(f"pz_mlp_backward failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+            *_launch.ptrs(xs), net.OBS_FORMATS[xs[0].dtype], n, K, obs_pitch, H, O, net.ACTIVATIONS[activation],
+            *[p.data_ptr() for p in sets[0]], *([p.data_ptr() for p in sets[1]] if two else [None] * 6), *_launch.ptrs(gs),
+            GRAD_FORMATS[gs[0].dtype], grad_pitch, *[t.data_ptr() for t in outs[0]],
+            *([t.data_ptr() for t in outs[1]] if groups == 2 else [None] * 6), ws.data_ptr(), _launch.raw_stream(index))
+    _launch.check(code, "pz_mlp_backward", _ERRORS)
     return result
 
 
@@ -238,8 +203,8 @@ def head(obs, params, activation: str = "tanh"):
     two agents on ONE parameter sequence (a shared net: the gradients of both agents' rows are summed).  ``obs`` gets no
     gradient.  An incoming gradient that is ``None`` counts as zeros; one whose last dimension is not contiguous or whose
     rows overlap (``expand``) is made contiguous first."""
-    keys, xs = net._sides(obs, "obs")
+    keys, xs = _launch.sides(obs, "obs")
     if isinstance(params, dict) or isinstance(params, torch.Tensor) or not hasattr(params, "__len__") or len(params) != 6:
         raise ValueError("params must be one sequence of six tensors (W1, b1, W2, b2, W3, b3)")
     ys = _Head.apply(activation, len(xs), *xs, *params)
-    return dict(zip(keys, ys)) if keys is not None else ys[0]
+    return _launch.shape(keys, ys)

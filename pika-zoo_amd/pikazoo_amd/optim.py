@@ -11,8 +11,8 @@ one or two nets, with the moments and the step count, in ONE launch on parameter
     optim.adam_step(params, grads, exp_avg, exp_avg_sq, step, lr=3e-4, max_grad_norm=0.5)     # the same without the class
 
 ctypes binding of libpikazoo_optim.so (C ABI and the definition: include/pikazoo_optim.h), a library of its own beside the
-product library; nothing in the step path, ``learn``, ``policy``, ``ppo``, ``net`` or ``netgrad`` imports this module.  There is
-no torch fallback: a missing or stale library raises.  The launch allocates nothing and does not synchronise: a captured graph
+product library; nothing in the step path, ``learn``, ``policy``, ``ppo``, ``net`` or ``netgrad`` imports this module, and it
+imports none of them.  There is no torch fallback: a missing or stale library raises.  The launch allocates nothing and does not synchronise: a captured graph
 can hold a whole minibatch update, the step count included (it lives in device memory), and a learning rate given as a device
 tensor is read at run time.  No atomics: the bits depend on the inputs only.  DEPARTURE from ``clip_grad_norm_``: gradients are
 read only; the clipped gradient is never written back to ``.grad``.
@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from . import _native, net
+from . import _launch, _native
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_optim.so"
 ABI_VERSION = 1
@@ -57,8 +57,7 @@ SIGNATURES = {
     # (groups, n_groups, cfg, stream)
     "pz_adam_step": (C.c_int, [C.POINTER(Group), C.c_int32, C.POINTER(Config), _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a group, tensor or element count beyond the kernel's range",
-           -3: "a hyperparameter out of range", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a group, tensor or element count beyond the kernel's range", -3: "a hyperparameter out of range"}
 _lib = None
 
 
@@ -132,8 +131,7 @@ def _words(x, what, keys, groups, dtype, dev):
         ts = [x]
     for t in ts:
         if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (2,) or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{what} must be a contiguous {dtype} tensor of two elements on {dev}, got "
-                             f"{type(t).__name__ if not isinstance(t, torch.Tensor) else f'{t.dtype} {list(t.shape)} on {t.device}'}")
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of two elements on {dev}, got {_launch.describe(t)}")
     return ts
 
 
@@ -183,7 +181,7 @@ def _plan(params, grads, exp_avg, exp_avg_sq, step, stats, cfg, lr_tensor):
     inputs = [(f"grads[{a}][{i}]", t) for a in range(n_groups) for i, t in enumerate(gs[a])]
     if lr_tensor is not None:
         inputs.append(("lr", lr_tensor))
-    net._no_alias(outputs, inputs)
+    _launch.no_alias(outputs, inputs)
     if dev.type != "cuda":
         raise ValueError(f"the optimizer step runs on the GPU: the parameters are on {dev}")
     array = (Group * MAX_GROUPS)()
@@ -198,14 +196,14 @@ def _plan(params, grads, exp_avg, exp_avg_sq, step, stats, cfg, lr_tensor):
     return array, n_groups, dev
 
 
-def _launch(array, n_groups, cfg, dev):
+def _run(array, n_groups, cfg, dev):
+    """the launch of a checked plan: what ``Adam.step()`` pays on every call"""
     lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    index = _launch.device_index(dev)
     with torch.cuda.device(index):
-        stream = net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-        code = lib.pz_adam_step(array, n_groups, C.byref(cfg), stream)
+        code = lib.pz_adam_step(array, n_groups, C.byref(cfg), _launch.raw_stream(index))
     if code != 0:
-        raise _native.PikazooNativeError(f"pz_adam_step failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+        _launch.check(code, "pz_adam_step", _ERRORS)
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, *, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
@@ -226,7 +224,7 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, step, *, lr, betas=(0.9, 0.999
     alias and range errors raise ``ValueError`` before the library is needed."""
     cfg, lr_tensor = _config(lr, betas, eps, weight_decay, decoupled, max_grad_norm, skip_nonfinite)
     array, n_groups, dev = _plan(params, grads, exp_avg, exp_avg_sq, step, stats, cfg, lr_tensor)
-    _launch(array, n_groups, cfg, dev)
+    _run(array, n_groups, cfg, dev)
 
 
 _OPTIONS = ("lr", "betas", "eps", "weight_decay", "decoupled", "max_grad_norm", "skip_nonfinite")
@@ -312,7 +310,7 @@ class Adam(torch.optim.Optimizer):
                 if len(self._plans) > 8:  # (gradients that move every step: keep the table small)
                     self._plans.pop(next(iter(self._plans)))
             array, n_groups, cfg, dev, _alive = plan
-            _launch(array, n_groups, cfg, dev)
+            _run(array, n_groups, cfg, dev)
         return loss
 
     def _make_plan(self, batch):

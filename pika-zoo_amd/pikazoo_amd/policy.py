@@ -18,7 +18,8 @@ from typing import Optional
 
 import torch
 
-from . import _native
+from . import _launch, _native
+from ._launch import ptrs as _ptrs, shape as _shape
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_policy.so"
 ABI_VERSION = 1
@@ -41,10 +42,8 @@ SIGNATURES = {
     "pz_action_log_probs_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
                                                _P, _P, _P, C.c_int64, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size, a pitch, a game id or a step beyond the kernel's range",
-           -3: "an unknown format", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size, a pitch, a game id or a step beyond the kernel's range", -3: "an unknown format"}
 _lib = None
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def load():
@@ -56,23 +55,9 @@ def load():
     return _lib
 
 
-def _sides(x, what):
-    """(keys or None, [tensor, ...]) of a tensor or an {agent: tensor} dict of one or two agents"""
-    if isinstance(x, dict):
-        if not 1 <= len(x) <= 2:
-            raise ValueError(f"{what}: a dict of one or two agents, got {len(x)}")
-        keys, vals = list(x), list(x.values())
-    else:
-        keys, vals = None, [x]
-    for v in vals:
-        if not isinstance(v, torch.Tensor):
-            raise ValueError(f"{what} must be a tensor or a dict of tensors, got {type(v).__name__}")
-    return keys, vals
-
-
 def _check_logits(logits):
     """(keys, tensors, n, A, pitch, device) of the logits of one or two agents"""
-    keys, ls = _sides(logits, "logits")
+    keys, ls = _launch.sides(logits, "logits")
     l0 = ls[0]
     if l0.dim() != 2:
         raise ValueError(f"logits must have shape [N, A], got {tuple(l0.shape)}")
@@ -99,7 +84,7 @@ def _check_logits(logits):
 
 def _vectors(x, what, keys, n, dtypes, dev):
     """the [n] tensors of `x` (in the shape of the logits: a dict with the same agents, or one tensor), contiguous"""
-    xkeys, ts = _sides(x, what)
+    xkeys, ts = _launch.sides(x, what)
     if xkeys != keys:
         raise ValueError(f"{what} must name the agents of the logits in their order: {keys}, got {xkeys}")
     for t in ts:
@@ -108,18 +93,6 @@ def _vectors(x, what, keys, n, dtypes, dev):
         if n > 1 and t.stride(0) != 1:
             raise ValueError(f"{what} must be contiguous (stride {t.stride(0)})")
     return ts
-
-
-def _stream(index):
-    return _get_raw_stream(index) if _get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-
-
-def _ptrs(ts):
-    return ts[0].data_ptr(), (ts[1].data_ptr() if len(ts) == 2 else None)
-
-
-def _shape(keys, ts):
-    return dict(zip(keys, ts)) if keys is not None else ts[0]
 
 
 def sample(logits, seed: int, step=0, first_game: int = 0, action_dtype=torch.int64, out: Optional[dict] = None):
@@ -166,14 +139,8 @@ def sample(logits, seed: int, step=0, first_game: int = 0, action_dtype=torch.in
         out = {"actions": _shape(keys, act), "log_probs": _shape(keys, logp), "entropy": _shape(keys, ent)}
     if n == 0:
         return out
-    lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_sample_actions(*_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch, seed, first_game, step,
-                                     step_dev.data_ptr() if step_dev is not None else None, ACTION_FORMATS[action_dtype],
-                                     *_ptrs(act), *_ptrs(logp), *_ptrs(ent), _stream(index))
-    if code != 0:
-        raise _native.PikazooNativeError(f"pz_sample_actions failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+    _launch.launch(load().pz_sample_actions, _ERRORS, dev, *_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch, seed, first_game, step,
+                   step_dev.data_ptr() if step_dev is not None else None, ACTION_FORMATS[action_dtype], *_ptrs(act), *_ptrs(logp), *_ptrs(ent))
     return out
 
 
@@ -181,13 +148,8 @@ def _forward(ls, act, n, A, pitch, dev):
     logp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in ls]
     ent = [torch.empty(n, dtype=torch.float32, device=dev) for _ in ls]
     if n:
-        lib = load()
-        index = dev.index if dev.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(index):
-            code = lib.pz_action_log_probs(*_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch, ACTION_FORMATS[act[0].dtype],
-                                           *_ptrs(act), *_ptrs(logp), *_ptrs(ent), _stream(index))
-        if code != 0:
-            raise _native.PikazooNativeError(f"pz_action_log_probs failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+        _launch.launch(load().pz_action_log_probs, _ERRORS, dev, *_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch,
+                       ACTION_FORMATS[act[0].dtype], *_ptrs(act), *_ptrs(logp), *_ptrs(ent))
     return logp, ent
 
 
@@ -218,16 +180,10 @@ class _LogProbs(torch.autograd.Function):
             return (None,) * (4 + 2 * sides)
         grad = [torch.empty((n, A), dtype=l.dtype, device=dev) for l in ls]
         if n:
-            lib = load()
-            index = dev.index if dev.index is not None else torch.cuda.current_device()
             none = (None, None)
-            with torch.cuda.device(index):
-                code = lib.pz_action_log_probs_backward(
-                    *_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch, ACTION_FORMATS[act[0].dtype], *_ptrs(act),
-                    *(_ptrs(glogp) if glogp is not None else none), *(_ptrs(gent) if gent is not None else none), *_ptrs(grad), A,
-                    _stream(index))
-            if code != 0:
-                raise _native.PikazooNativeError(f"pz_action_log_probs_backward failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
+            _launch.launch(load().pz_action_log_probs_backward, _ERRORS, dev, *_ptrs(ls), LOGIT_FORMATS[ls[0].dtype], A, n, pitch,
+                           ACTION_FORMATS[act[0].dtype], *_ptrs(act), *(_ptrs(glogp) if glogp is not None else none),
+                           *(_ptrs(gent) if gent is not None else none), *_ptrs(grad), A)
         return (None, None, None, None, *([None] * sides), *grad)
 
 

@@ -12,10 +12,11 @@ through the parameter set of its own pool member.
     pool.forward(obs, member_params, plans)                     # the same launch on any P parameter sets
 
 ctypes binding of libpikazoo_pool.so (C ABI and the definition: include/pikazoo_pool.h), a library of its own beside the
-product library; nothing in the step path or in the other modules imports this one.  There is no torch fallback: a missing or
+product library; nothing in the step path or in the other modules imports this one (``league`` does, on first use).  There is no torch fallback: a missing or
 stale library raises.  A row's result holds exactly the bits ``net.forward`` gives it with its member's parameters.  The
 parameters are read in place from up to 16 sets of ``nn.Linear`` tensors, so an optimizer step on member 0 is seen by the
-next launch, and by the next replay of a captured graph.
+next launch, and by the next replay of a captured graph.  The arguments are checked by ``net``'s own check, a member's name in
+front of its tensor's; the launch plumbing is ``_launch``'s.
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ import ctypes as C
 
 import torch
 
-from . import _native, net
+from . import _launch, _native, net
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_pool.so"
 ABI_VERSION = 1
@@ -52,8 +53,7 @@ SIGNATURES = {
     "pz_mlp_forward_pool": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Member),
                                       C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size, a pitch or the number of members beyond the kernel's range",
-           -3: "an unknown format or activation", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size, a pitch or the number of members beyond the kernel's range", -3: "an unknown format or activation"}
 _lib = None
 
 
@@ -69,15 +69,6 @@ def load():
 def capacity(n: int, num_members: int) -> int:
     """the int32 words of a plan's ``order``: ``(n // 128 + num_members) * 128`` (include/pikazoo_pool.h proves the bound)"""
     return (n // GROUP_ROWS + num_members) * GROUP_ROWS
-
-
-def _stream(index):
-    return net._get_raw_stream(index) if net._get_raw_stream is not None else torch.cuda.current_stream(index).cuda_stream
-
-
-def _check(code, name):
-    if code != 0:
-        raise _native.PikazooNativeError(f"{name} failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
 
 
 # ---- the plan ------------------------------------------------------------------------------------------------------------------
@@ -126,18 +117,14 @@ def plan(members, num_members, out=None) -> Plan:
             if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (size,) or not t.is_contiguous()
                     or t.device != dev):
                 raise ValueError(f"out.{name} must be a contiguous int32 [{size}] tensor on {dev}")
-        net._no_alias([("out.order", out.order), ("out.first", out.first), ("out.errors", out.errors)], [("members", members)])
+        _launch.no_alias([("out.order", out.order), ("out.first", out.first), ("out.errors", out.errors)], [("members", members)])
     if dev.type != "cuda":
         raise ValueError(f"the plan is built on the GPU: members are on {dev}")
     if out is None:
         out = Plan(torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(num_members + 1, dtype=torch.int32, device=dev),
                    torch.empty(1, dtype=torch.int32, device=dev), n, num_members)
-    lib = load()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_pool_plan(members.data_ptr() if n else None, MEMBER_FORMATS[members.dtype], n, num_members, out.order.data_ptr(),
-                                out.first.data_ptr(), out.errors.data_ptr(), _stream(index))
-    _check(code, "pz_pool_plan")
+    _launch.launch(load().pz_pool_plan, _ERRORS, dev, members.data_ptr() if n else None, MEMBER_FORMATS[members.dtype], n, num_members,
+                   out.order.data_ptr(), out.first.data_ptr(), out.errors.data_ptr())
     return out
 
 
@@ -195,79 +182,30 @@ def forward(obs, member_params, plans, activation: str = "tanh", out=None, out_d
 
     The launch goes to the current stream without a synchronisation and can be captured.  Shape, dtype, device and range
     errors raise ``ValueError`` before any launch."""
-    keys, xs = net._sides(obs, "obs")
-    x0 = xs[0]
-    if x0.dim() != 2:
-        raise ValueError(f"obs must have shape [N, K], got {tuple(x0.shape)}")
-    n, K, dev = int(x0.shape[0]), int(x0.shape[1]), x0.device
-    if not 1 <= K <= net.MAX_IN:
-        raise ValueError(f"obs: 1 <= K <= {net.MAX_IN} features, got {K}")
-    if n > MAX_ROWS:
-        raise ValueError(f"obs: at most 2^30 rows, got {n}")
-    if x0.dtype not in net.OBS_FORMATS:
-        raise ValueError(f"obs must be {' or '.join(str(d) for d in net.OBS_FORMATS)}, got {x0.dtype}")
-    obs_pitch = net._rows(xs, "obs", n, K, tuple(net.OBS_FORMATS), dev)
-    if activation not in net.ACTIVATIONS:
-        raise ValueError(f"activation must be {' or '.join(repr(a) for a in net.ACTIVATIONS)}, got {activation!r}")
+    keys, xs, n, K, dev, obs_pitch = net._observations(obs, activation)
     sets = _member_sets(member_params)
-    P = len(sets)
-    w1 = sets[0][0]
-    if w1.dim() != 2:
-        raise ValueError(f"W1 must have shape [hidden, {K}], got {tuple(w1.shape)}")
-    H = int(w1.shape[0])
-    if H not in net.HIDDEN:
-        raise ValueError(f"hidden must be one of {net.HIDDEN}, got {H}")
-    w3 = sets[0][4]
-    if w3.dim() != 2:
-        raise ValueError(f"W3 must have shape [out_features, {H}], got {tuple(w3.shape)}")
-    O = int(w3.shape[0])
-    if not 1 <= O <= net.MAX_OUT:
-        raise ValueError(f"1 <= out_features <= {net.MAX_OUT}, got {O}")
-    names = ("W1", "b1", "W2", "b2", "W3", "b3")
-    shapes = ((H, K), (H,), (H, H), (H,), (O, H), (O,))
-    for m, ps in enumerate(sets):
-        for name, shape, p in zip(names, shapes, ps):
-            if tuple(p.shape) != shape or p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise ValueError(f"member {m}: {name} must be a contiguous float32 {list(shape)} tensor on {dev}, got {p.dtype} "
-                                 f"{list(p.shape)} on {p.device}{'' if p.is_contiguous() else ', not contiguous'}")
-    per = _agent_plans(plans, keys, len(xs), n, P, dev)
-    if out is not None:
-        okeys, ys = net._sides(out, "out")
-        if okeys != keys:
-            raise ValueError(f"out must name the agents of obs in their order: {keys}, got {okeys}")
-        if ys[0].dtype not in net.OUT_FORMATS:
-            raise ValueError(f"out must be {' or '.join(str(d) for d in net.OUT_FORMATS)}, got {ys[0].dtype}")
-        out_pitch = net._rows(ys, "out", n, O, tuple(net.OUT_FORMATS), dev)
-    else:
-        if out_dtype not in net.OUT_FORMATS:
-            raise ValueError(f"out_dtype must be {' or '.join(str(d) for d in net.OUT_FORMATS)}, got {out_dtype}")
-        ys = None
-        out_pitch = O
+    H, O, _ = net._box(sets, K, dev, "member {}: ")
+    per = _agent_plans(plans, keys, len(xs), n, len(sets), dev)
+    ys, out_pitch = net._outputs(out, out_dtype, keys, n, O, dev)
     if dev.type != "cuda":
         raise ValueError(f"the policy net runs on the GPU: obs are on {dev}")
     if ys is None:
         ys = [torch.empty((n, O), dtype=out_dtype, device=dev) for _ in xs]
-        out = net._shape(keys, ys)
-    net._no_alias([(f"out[{s}]", y) for s, y in enumerate(ys)],
-                  [(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"member {m} {name}", p) for m, ps in enumerate(sets) for name, p in zip(names, ps)]
-                  + [(f"plans[{s}].{name}", t) for s, p in enumerate(per) if p is not None for name, t in (("order", p.order), ("first", p.first))])
+        out = _launch.shape(keys, ys)
+    _launch.no_alias([(f"out[{s}]", y) for s, y in enumerate(ys)],
+                     [(f"obs[{s}]", x) for s, x in enumerate(xs)] + [(f"member {m} {name}", p) for m, ps in enumerate(sets) for name, p in zip(net.NAMES, ps)]
+                     + [(f"plans[{s}].{name}", t) for s, p in enumerate(per) if p is not None for name, t in (("order", p.order), ("first", p.first))])
     if n == 0:
         return out
-    lib = load()
     array = (Member * MAX_MEMBERS)()
     for m, ps in enumerate(sets):
         array[m] = Member(*[p.data_ptr() for p in ps])
-    two = len(xs) == 2
     plan_ptrs = []
     for s in range(2):
         p = per[s] if s < len(per) else None
         plan_ptrs += [p.order.data_ptr(), p.first.data_ptr()] if p is not None else [None, None]
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(index):
-        code = lib.pz_mlp_forward_pool(xs[0].data_ptr(), xs[1].data_ptr() if two else None, net.OBS_FORMATS[x0.dtype], n, K, obs_pitch, H, O,
-                                       net.ACTIVATIONS[activation], array, P, *plan_ptrs, ys[0].data_ptr(), ys[1].data_ptr() if two else None,
-                                       net.OUT_FORMATS[ys[0].dtype], out_pitch, _stream(index))
-    _check(code, "pz_mlp_forward_pool")
+    _launch.launch(load().pz_mlp_forward_pool, _ERRORS, dev, *_launch.ptrs(xs), net.OBS_FORMATS[xs[0].dtype], n, K, obs_pitch, H, O,
+                   net.ACTIVATIONS[activation], array, len(sets), *plan_ptrs, *_launch.ptrs(ys), net.OUT_FORMATS[ys[0].dtype], out_pitch)
     return out
 
 

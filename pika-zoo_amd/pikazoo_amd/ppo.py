@@ -8,7 +8,7 @@ statistics and its gradients with respect to the logits and the values from ONE 
 ctypes binding of libpikazoo_ppo.so (C ABI and the definition: include/pikazoo_ppo.h), a library of its own beside the
 product library; nothing in the step path, ``learn`` or ``policy`` imports this module.  There is no torch fallback: a
 missing or stale library raises.  The reductions are deterministic (no floating-point atomics): two calls on the same
-inputs return the same bits.
+inputs return the same bits.  ``_check_logits`` and ``_vectors`` are ``policy``'s, the launch plumbing is ``_launch``'s.
 """
 from __future__ import annotations
 
@@ -18,8 +18,9 @@ from typing import Optional
 
 import torch
 
-from . import _native
-from .policy import ACTION_FORMATS, LOGIT_FORMATS, _check_logits, _ptrs, _shape, _sides, _stream, _vectors
+from . import _launch, _native
+from ._launch import ptrs as _ptrs, shape as _shape, sides as _sides
+from .policy import ACTION_FORMATS, LOGIT_FORMATS, _check_logits, _vectors
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_ppo.so"
 ABI_VERSION = 1
@@ -44,8 +45,7 @@ SIGNATURES = {
                               C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
                               C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
 }
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size or a pitch beyond the kernel's range",
-           -3: "an unknown format or a coefficient outside its range", -4: "a pointer not aligned to its element"}
+_ERRORS = {**_launch.ERRORS, -2: "a size or a pitch beyond the kernel's range", -3: "an unknown format or a coefficient outside its range"}
 _lib = None
 
 
@@ -72,37 +72,6 @@ def _workspace(n, dev):
     return torch.empty(max(workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
 
 
-def _check_workspace(ws, n, dev):
-    if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or ws.dim() != 1 or ws.stride(0) != 1
-            or ws.numel() < workspace_bytes(n) or ws.data_ptr() % 16):
-        raise ValueError(f"the workspace must be a contiguous uint8 tensor of at least {workspace_bytes(n)} bytes on {dev}, aligned to 16")
-    return ws
-
-
-def _fail(name, code):
-    raise _native.PikazooNativeError(f"{name} failed: {_ERRORS.get(code, 'HIP error')} (code {code})")
-
-
-def _index(dev):
-    return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
-def _span(t):
-    """[first byte, last byte + 1) of the memory a tensor's elements lie in"""
-    if t.numel() == 0:
-        return t.data_ptr(), t.data_ptr()
-    return t.data_ptr(), t.data_ptr() + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
-
-
-def _no_alias(outputs, inputs):
-    spans = [(what, _span(t)) for what, t in inputs]
-    for i, (what, t) in enumerate(outputs):
-        lo, hi = _span(t)
-        for other, (olo, ohi) in spans + [(w, _span(u)) for w, u in outputs[:i]]:
-            if lo < ohi and olo < hi:
-                raise ValueError(f"{what} overlaps {other}: outputs must not alias an input or each other")
-
-
 def moments(advantages, eps: float = 1e-8, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
     """``[sides, 2]`` float32 on the device: ``(mean, 1 / (std + eps))`` of each agent's float32 ``[N]`` vector, ``std`` the
     unbiased deviation -- what ``(adv - adv.mean()) / (adv.std() + 1e-8)`` uses (``pz_ppo_moments``; accumulated in float64
@@ -126,14 +95,9 @@ def moments(advantages, eps: float = 1e-8, out: Optional[torch.Tensor] = None, w
         out = torch.empty((len(xs), 2), dtype=torch.float32, device=dev)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (len(xs), 2) or out.device != dev or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 [{len(xs)}, 2] tensor on {dev}")
-    ws = _workspace(n, dev) if workspace is None else _check_workspace(workspace, n, dev)
-    _no_alias([("out", out), ("workspace", ws)], [("advantages", x) for x in xs])
-    lib = load()
-    index = _index(dev)
-    with torch.cuda.device(index):
-        code = lib.pz_ppo_moments(*_ptrs(xs), n, eps, out.data_ptr(), ws.data_ptr(), _stream(index))
-    if code != 0:
-        _fail("pz_ppo_moments", code)
+    ws = _workspace(n, dev) if workspace is None else _launch.check_workspace(workspace, workspace_bytes(n), dev)
+    _launch.no_alias([("out", out), ("workspace", ws)], [("advantages", x) for x in xs])
+    _launch.launch(load().pz_ppo_moments, _ERRORS, dev, *_ptrs(xs), n, eps, out.data_ptr(), ws.data_ptr())
     return out
 
 
@@ -224,7 +188,7 @@ def loss_and_grad(logits=None, values=None, actions=None, old_log_probs=None, ad
     if out is not None:
         if not isinstance(out, dict) or "_stats" not in out or "workspace" not in out or "adv_norm" not in out:
             raise ValueError("out must be the result of an earlier call")
-        raw, ws, norm = out["_stats"], _check_workspace(out["workspace"], n, dev), out["adv_norm"]
+        raw, ws, norm = out["_stats"], _launch.check_workspace(out["workspace"], workspace_bytes(n), dev), out["adv_norm"]
         if raw.dtype != torch.float32 or tuple(raw.shape) != (2, 8) or raw.device != dev or not raw.is_contiguous():
             raise ValueError(f"out['_stats'] must be a contiguous float32 [2, 8] tensor on {dev}")
         if norm.dtype != torch.float32 or tuple(norm.shape) != (2, 2) or norm.device != dev or not norm.is_contiguous():
@@ -266,25 +230,22 @@ def loss_and_grad(logits=None, values=None, actions=None, old_log_probs=None, ad
     outputs += [("stats", raw), ("workspace", ws), ("adv_norm", norm)]
     inputs = [(what, t) for what, ts in (("logits", ls), ("values", vs), ("actions", act), ("old_log_probs", old_lp), ("advantages", adv),
                                          ("returns", ret), ("old_values", old_vs or [])) for t in ts]
-    _no_alias(outputs, inputs)
+    _launch.no_alias(outputs, inputs)
     if n == 0:
         return out
     lib = load()
-    index = _index(dev)
+    index = _launch.device_index(dev)
     none = (None, None)
-    with torch.cuda.device(index):
-        stream = _stream(index)
+    with torch.cuda.device(index):  # (both launches under one guard, on one stream)
+        stream = _launch.raw_stream(index)
         if normalize_advantages:
-            code = lib.pz_ppo_moments(*_ptrs(adv), n, 1e-8, norm.data_ptr(), ws.data_ptr(), stream)
-            if code != 0:
-                _fail("pz_ppo_moments", code)
+            _launch.check(lib.pz_ppo_moments(*_ptrs(adv), n, 1e-8, norm.data_ptr(), ws.data_ptr(), stream), "pz_ppo_moments", _ERRORS)
         code = lib.pz_ppo_loss(*_ptrs(ls), LOGIT_FORMATS[grad_dtype], A, n, pitch, ACTION_FORMATS[act[0].dtype], *_ptrs(act), *_ptrs(old_lp),
                                *_ptrs(adv), *_ptrs(ret), *_ptrs(vs), VALUE_FORMATS[value_dtype], value_pitch,
                                *(_ptrs(old_vs) if old_vs is not None else none), VALUE_FORMATS[old_vs[0].dtype] if old_vs is not None else 0,
                                norm.data_ptr() if normalize_advantages else None, clip, value_clip, vf_coef, ent_coef, *_ptrs(gls),
                                grad_pitch, *_ptrs(gvs), grad_value_pitch, raw.data_ptr(), ws.data_ptr(), stream)
-    if code != 0:
-        _fail("pz_ppo_loss", code)
+    _launch.check(code, "pz_ppo_loss", _ERRORS)
     return out
 
 
