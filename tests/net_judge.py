@@ -142,6 +142,17 @@ def make_obs(n, K, dtype, seed):
     return J.as_logit_dtype(rng.uniform(0, 1, (n, K)).astype(np.float32), dtype)
 
 
+def exact_matmul(a, b):
+    """a @ b of integer matrices as int64, through a float64 BLAS call (numpy's int64 product takes seconds at the batch sizes
+    of the large cases): every product and every partial sum, in any order, is an integer below 2^53 and so an exact float64
+    -- asserted on the bound (inner dimension) x max |a| x max |b|"""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.dtype.kind == "i" and b.dtype.kind == "i"
+    if a.size and b.size:
+        assert a.shape[-1] * int(np.abs(a).max()) * int(np.abs(b).max()) < 2 ** 53
+    return (a.astype(np.float64) @ b.astype(np.float64)).astype(np.int64)
+
+
 def integer_case(n, K, H, O, seed=5):
     """small integers for relu: weights in [-3, 3] (drawn, so W[i][k] != W[k][i] and no two rows or columns agree), biases in
     [-2, 2], observations in [-2, 4].  Every float32 sum is exact, so the output EQUALS the integer result (int64 here):
@@ -153,7 +164,7 @@ def integer_case(n, K, H, O, seed=5):
     x = rng.integers(-2, 5, (n, K))
     h = x
     for layer in range(3):
-        h = h @ params[2 * layer].T + params[2 * layer + 1]
+        h = exact_matmul(h, params[2 * layer].T) + params[2 * layer + 1]
         if layer < 2:
             h = np.maximum(h, 0)
             assert np.abs(h).max() < 2 ** 24 // max(H, K) // 4  # every partial sum of the next layer stays an exact float32

@@ -42,14 +42,28 @@ def _product(a, ea, b, eb, m):
     return a.T @ b, (1 + g) * (A.T @ eb + ea.T @ B + ea.T @ eb) + g * (A.T @ B)
 
 
-def judge(sides, params, activation):
+def documented_roundings(n, hidden, cus, shared=False):
+    """the most roundings a row's term passes through in a sum over the rows, by the sentence of include/pikazoo_netgrad.h: a
+    workgroup takes passes of R = 128 / hidden * 32 rows, there are B = min(passes, compute units) workgroups per agent, so a
+    workgroup holds at most ceil(passes / B) passes: (rows of its workgroup) + (workgroups - 1) + (1 for a shared net).  `n` is
+    the number of rows of ONE agent."""
+    R = 32 * (128 // hidden)
+    passes = -(-n // R)
+    B = min(passes, cus)
+    return -(-passes // B) * R + (B - 1) + int(bool(shared))
+
+
+def judge(sides, params, activation, roundings=None):
     """(six float64 gradients, six tolerances, the number of ambiguous relu units) of `sides` = [(obs [n, K], grad_head [n, O]),
     ...] under `params` = (W1, b1, W2, b2, W3, b3): the gradients are summed over all rows of all sides (a shared net); judge
-    one side at a time for separate nets."""
+    one side at a time for separate nets.  `roundings` is the m of the sums over the rows: by default the number of rows, which
+    holds for every order of summation; `documented_roundings` gives the header's own, smaller count, under which a large
+    batch's tolerance still sees a lost pass."""
     x = np.concatenate([np.asarray(o) for o, _ in sides])
     d3 = np.concatenate([np.asarray(g, np.float64) for _, g in sides])
     W1, b1, W2, b2, W3, b3 = (np.asarray(p, np.float64) for p in params)
     n = x.shape[0]
+    roundings = n if roundings is None else roundings
     with np.errstate(invalid="ignore", over="ignore"):
         h0 = x.astype(np.float64)
         e0 = np.abs(h0 - h0.astype(np.float32).astype(np.float64)) if x.dtype.kind == "i" else np.zeros_like(h0)
@@ -86,7 +100,7 @@ def judge(sides, params, activation):
         grads, tols = [], []
         for d, ed, h, eh in ((d1, e1, hs[0], ehs[0]), (d2, e2, hs[1], ehs[1]), (d3, e3, hs[2], ehs[2])):
             for b, eb in ((h, eh), (one, zero)):
-                ref, tol = _product(d, ed, b, eb, n)
+                ref, tol = _product(d, ed, b, eb, roundings)
                 grads.append(ref if b is h else ref[:, 0])
                 tols.append(tol if b is h else tol[:, 0])
     return grads, tols, ambiguous
@@ -124,53 +138,61 @@ def worst_share(have, refs, tols):
     return worst, beyond
 
 
+def _row_chain32(obs, grad, params, activation, mutant=None):
+    """the per-row half of the float32 restatement: [(d1, x), (d2, h1), (d3, h2)], each row's factors of the three weight
+    gradients, every inner product a chain of fused multiply-adds in index order"""
+    f = np.float32
+    bf = lambda v: J.from_bfloat16_bits(J.to_bfloat16_bits(np.asarray(v, f)))  # noqa: E731
+    W1, b1, W2, b2, W3, b3 = (np.asarray(p, f) for p in params)
+    x, d3 = np.asarray(obs).astype(f), np.asarray(grad).astype(f)
+
+    def dense(h, W, b):
+        acc = np.broadcast_to(b, (h.shape[0], W.shape[0])).astype(f)
+        for k in range(W.shape[1]):
+            acc = N.fma32(h[:, k:k + 1], W[None, :, k], acc)
+        return acc
+
+    def act(z):
+        h = np.where(z < 0, f(0), z) if activation == "relu" else np.tanh(z.astype(np.float64)).astype(f)
+        return bf(h) if mutant == "bfloat16_hidden" else h
+
+    def factor(z, h):
+        if activation == "tanh":
+            return (f(1) - h) if mutant == "tanh_derivative_not_squared" else (f(1) - h * h).astype(f)
+        if mutant == "relu_derivative_one_at_zero":
+            return np.where(z < 0, f(0), f(1))
+        return np.where(z <= 0, f(0), f(1))
+
+    z1 = dense(x, W1, b1)
+    h1 = act(z1)
+    z2 = dense(h1, W2, b2)
+    h2 = act(z2)
+    W3b = W3
+    if mutant == "w3_columns_swapped":
+        W3b = W3.copy()
+        W3b[:, [0, 1]] = W3b[:, [1, 0]]
+    d2 = (dense(d3, W3b.T.copy(), f(0)) * factor(z2, h2)).astype(f)
+    d1 = (dense(d2, W2.T.copy(), f(0)) * factor(z1, h1)).astype(f)
+    return [(d1, x), (d2, h1), (d3, h2)]
+
+
 def restate_float32(sides, params, activation, order=None, mutant=None):
     """the definition as float32 arithmetic gives it: every inner product a chain of fused multiply-adds, the rows summed in
     index order or, with `order` = a numpy Generator, in a drawn order; a shared net's sides are summed one after the other.
     It takes the mutants too.  Six float32 arrays."""
     f = np.float32
-    bf = lambda v: J.from_bfloat16_bits(J.to_bfloat16_bits(np.asarray(v, f)))  # noqa: E731
-    W1, b1, W2, b2, W3, b3 = (np.asarray(p, f) for p in params)
     total = None
     for index, (obs, grad) in enumerate(sides):
         if mutant == "agent2_not_summed" and index == 1:
             continue
-        x, d3 = np.asarray(obs).astype(f), np.asarray(grad).astype(f)
         if mutant == "last_row_dropped":
-            x, d3 = x[:-1], d3[:-1]
-
-        def dense(h, W, b):
-            acc = np.broadcast_to(b, (h.shape[0], W.shape[0])).astype(f)
-            for k in range(W.shape[1]):
-                acc = N.fma32(h[:, k:k + 1], W[None, :, k], acc)
-            return acc
-
-        def act(z):
-            h = np.where(z < 0, f(0), z) if activation == "relu" else np.tanh(z.astype(np.float64)).astype(f)
-            return bf(h) if mutant == "bfloat16_hidden" else h
-
-        def factor(z, h):
-            if activation == "tanh":
-                return (f(1) - h) if mutant == "tanh_derivative_not_squared" else (f(1) - h * h).astype(f)
-            if mutant == "relu_derivative_one_at_zero":
-                return np.where(z < 0, f(0), f(1))
-            return np.where(z <= 0, f(0), f(1))
-
-        z1 = dense(x, W1, b1)
-        h1 = act(z1)
-        z2 = dense(h1, W2, b2)
-        h2 = act(z2)
-        W3b = W3
-        if mutant == "w3_columns_swapped":
-            W3b = W3.copy()
-            W3b[:, [0, 1]] = W3b[:, [1, 0]]
-        d2 = (dense(d3, W3b.T.copy(), f(0)) * factor(z2, h2)).astype(f)
-        d1 = (dense(d2, W2.T.copy(), f(0)) * factor(z1, h1)).astype(f)
-        rows = np.arange(x.shape[0])
+            obs, grad = np.asarray(obs)[:-1], np.asarray(grad)[:-1]
+        pairs = _row_chain32(obs, grad, params, activation, mutant)
+        rows = np.arange(pairs[0][0].shape[0])
         if order is not None:
             rows = order.permutation(rows)
         out = []
-        for d, h in ((d1, x), (d2, h1), (d3, h2)):
+        for d, h in pairs:
             dw, db = np.zeros((d.shape[1], h.shape[1]), f), np.zeros(d.shape[1], f)
             for r in rows:
                 dw = N.fma32(d[r][:, None], h[r][None, :], dw)
@@ -180,6 +202,57 @@ def restate_float32(sides, params, activation, order=None, mutant=None):
             out[3] = np.zeros_like(out[3])
         total = out if total is None else [(a + b).astype(f) for a, b in zip(total, out)]
     return total
+
+
+def restate_float32_in_pass_order(sides, params, activation, cus):
+    """the float32 restatement with the rows summed in the ORDER include/pikazoo_netgrad.h documents: passes of R = 128 / hidden
+    * 32 consecutive rows, B = min(passes, cus) workgroups per agent, workgroup b summing the rows of its passes p = b, b + B,
+    ... one after the other into a partial sum; the partials added in index order; a shared net's second agent's total added
+    last.  (All workgroups advance together here, one row at a time: the chains are independent.)  Six float32 arrays."""
+    f = np.float32
+    H = np.asarray(params[0]).shape[0]
+    R = 32 * (128 // H)
+    total = None
+    for obs, grad in sides:
+        pairs = _row_chain32(obs, grad, params, activation)
+        n = pairs[0][0].shape[0]
+        passes = -(-n // R)
+        B = min(passes, cus)
+        out = []
+        for d, h in pairs:
+            dw, db = np.zeros((B, d.shape[1], h.shape[1]), f), np.zeros((B, d.shape[1]), f)
+            for first in range(0, passes, B):                        # the workgroups' turn-th passes
+                for r in range(R):
+                    rows = (first + np.arange(B)) * R + r
+                    at = np.flatnonzero(rows < n)                    # (workgroups without this pass, or behind row n - 1: +0)
+                    if not len(at):
+                        break
+                    dr, hr = d[rows[at]], h[rows[at]]
+                    dw[at] = N.fma32(dr[:, :, None], hr[:, None, :], dw[at])
+                    db[at] = (db[at] + dr).astype(f)
+            w, b = dw[0], db[0]
+            for k in range(1, B):
+                w, b = (w + dw[k]).astype(f), (b + db[k]).astype(f)
+            out += [w, b]
+        total = out if total is None else [(a + b).astype(f) for a, b in zip(total, out)]
+    return total
+
+
+PASS_MUTANTS = ("a_pass_dropped", "a_pass_counted_twice", "partial_last_pass_dropped")
+
+
+def pass_mutant_rows(n, hidden, mutant, which=1):
+    """the rows a kernel with a broken pass loop would sum, as indices into the n rows: pass `which` missing, pass `which` twice,
+    or the partial pass at the end missing"""
+    R = 32 * (128 // hidden)
+    rows = np.arange(n)
+    own = (rows >= which * R) & (rows < (which + 1) * R)
+    if mutant == "a_pass_dropped":
+        return rows[~own]
+    if mutant == "a_pass_counted_twice":
+        return np.concatenate([rows, rows[own]])
+    assert mutant == "partial_last_pass_dropped" and n % R
+    return rows[:n - n % R]
 
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------
@@ -246,17 +319,18 @@ def integer_case(n, K, H, O, seed=5, small=False):
     x = rng.integers(lo, hi, (n, K))
     d3 = rng.integers(-g, g + 1, (n, O))
     limit = 2 ** 24
-    z1 = x @ W1.T + b1
+    mm = N.exact_matmul  # (int64 results through float64 BLAS: exact below 2^53, which it asserts)
+    z1 = mm(x, W1.T) + b1
     h1 = np.maximum(z1, 0)
-    z2 = h1 @ W2.T + b2
+    z2 = mm(h1, W2.T) + b2
     h2 = np.maximum(z2, 0)
-    assert (np.abs(x) @ np.abs(W1).T + np.abs(b1)).max() < limit and (h1 @ np.abs(W2).T + np.abs(b2)).max() < limit
+    assert (mm(np.abs(x), np.abs(W1).T) + np.abs(b1)).max() < limit and (mm(h1, np.abs(W2).T) + np.abs(b2)).max() < limit
     assert ((z1 == 0).sum() + (z2 == 0).sum()) > 0
-    d2 = (d3 @ W3) * (z2 > 0)
-    d1 = (d2 @ W2) * (z1 > 0)
-    assert (np.abs(d3) @ np.abs(W3)).max() < limit and (np.abs(d2) @ np.abs(W2)).max() < limit
+    d2 = mm(d3, W3) * (z2 > 0)
+    d1 = mm(d2, W2) * (z1 > 0)
+    assert mm(np.abs(d3), np.abs(W3)).max() < limit and mm(np.abs(d2), np.abs(W2)).max() < limit
     out = []
     for d, h in ((d1, x), (d2, h1), (d3, h2)):
-        assert (np.abs(d).T @ np.abs(h)).max() < limit and np.abs(d).sum(axis=0).max() < limit
-        out += [d.T @ h, d.sum(axis=0)]
+        assert mm(np.abs(d).T, np.abs(h)).max() < limit and np.abs(d).sum(axis=0).max() < limit
+        out += [mm(d.T, h), d.sum(axis=0)]
     return x, [np.asarray(p, np.float32) for p in params], d3, out

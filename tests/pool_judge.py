@@ -191,6 +191,13 @@ def forward_cases():
         c(obs_dtype="int16", n=4099, P=16, kinds=("invalid_entries", "one_member_empty")),
         c(n=128, P=1, kinds=("all_one_member", None)),
         c(n=40000, P=16, kinds=("invalid_entries", "round_robin")),          # more groups than resident workgroups: re-staging
+        # Sized for a grid cap of at most 256 compute units (`max_cus`, which the GPU test asserts).  H = 128 holds one
+        # workgroup per compute unit, two agents share them: at most 128 workgroups for the unplanned side's 157 groups of
+        # all rows, so some workgroups walk two groups with order == NULL ...
+        c(K=72, H=128, O=40, n=20000, P=3, kinds=(None, "sorted"), obs_extra=1, out_extra=2, offset=1, max_cus=256),
+        # ... and H = 32, two workgroups per compute unit: at most 256 for 313 plain groups and as many planned ones
+        c(H=32, activation="relu", obs_dtype="float16", n=40000, P=4, kinds=("reverse_sorted", None), obs_extra=2, out_extra=1, offset=1,
+          max_cus=256),
     ]
 
 

@@ -222,6 +222,54 @@ def test_bits_do_not_depend_on_the_batch(lib):
     assert np.array_equal(bits(single[0]), bits(whole[0][77:78]))
 
 
+def rows_past_the_first_tile():
+    """(compute units, n): the rule is pz_mlp_tile.hpp's grid cap -- at most two resident workgroups per compute unit, so no
+    launch has more than 2 CUs workgroups of four 32-row tiles, 2 CUs * 128 rows a trip of the tile loop.  Twice that, one
+    more workgroup's worth and 37 rows: every wave takes at least two tiles at every hidden width and either agent count
+    (a smaller cap only adds trips), the workgroups' tile counts differ, and the last tile has 5 live rows."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return cus, 2 * (2 * cus) * 128 + 128 + 37
+
+
+LARGE_SIZES = {32: (35, 32, 19), 64: (35, 64, 19), 128: (72, 128, 40)}
+
+
+@pytest.mark.parametrize("H", sorted(LARGE_SIZES))
+def test_every_wave_past_its_first_tile(lib, H):
+    """one agent and two agents on nets of their own at a batch beyond what the capped grid covers in one trip: every row
+    within the float64 judge's tolerance; three shards of 4096 rows -- the head, a span that starts behind the widest
+    first trip, the tail -- launched alone return the bits of the same rows of the whole launch"""
+    K, _, O = LARGE_SIZES[H]
+    cus, n = rows_past_the_first_tile()
+    print(f"{cus} compute units: n = {n}")
+    acts = ("tanh", "relu") if H != 64 else ("relu", "tanh")         # (both activations at both agent counts over the three H)
+    params = [N.make_params(K, H, O, seed) for seed in (24, 25)]
+    obs = [N.make_obs(n, K, "float32", seed) for seed in (26, 27)]
+    pitches = dict(obs_pitch=K + 3, out_pitch=O + 2, offset=1)
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint32)  # noqa: E731
+    spans = (0, 2 * cus * 128 + 33, n - 4096)
+    for sides, activation in zip((1, 2), acts):
+        whole = run_forward(lib, obs[:sides], "float32", params[:sides], activation, **pitches)
+        for s in range(sides):
+            check(whole[s], obs[s], params[s], activation, what=f"H = {H} n = {n} {activation} {sides} agent(s) side {s}")
+        for g0 in spans:
+            shard = run_forward(lib, [x[g0:g0 + 4096] for x in obs[:sides]], "float32", params[:sides], activation, **pitches)
+            for s in range(sides):
+                assert np.array_equal(bits(shard[s]), bits(whole[s][g0:g0 + 4096])), (H, sides, g0, s)
+
+
+@pytest.mark.parametrize("H", sorted(LARGE_SIZES))
+def test_exact_integers_past_the_first_tile(lib, H):
+    """the integer case at the same n: every row of every trip of the tile loop EQUALS the integer result"""
+    K, _, O = LARGE_SIZES[H]
+    cus, n = rows_past_the_first_tile()
+    print(f"{cus} compute units: n = {n}")
+    x, params, want = N.integer_case(n, K, H, O)
+    for dtype in ("int32", "float32"):
+        have = run_forward(lib, [x], dtype, [params], "relu", obs_pitch=K + 2)[0]
+        assert np.isfinite(have).all() and np.array_equal(have.astype(np.int64), want), (H, dtype)
+
+
 def test_bits_are_the_recorded_ones(lib):
     """tests/golden/net_forward_bits.json (tests/capture_net_bits.py) holds digests of what pz_mlp_forward wrote, taken from
     the library before its tile moved into csrc/pz_mlp_tile.hpp: every case must give those bits.  Every other test here

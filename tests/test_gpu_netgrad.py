@@ -11,7 +11,7 @@ import pytest
 
 import net_judge as N
 import netgrad_judge as G
-from test_netgrad_host import GPU_BATCHES, GPU_LAYERS, GPU_SEED
+from test_netgrad_host import GPU_BATCHES, GPU_LAYERS, GPU_SEED, LARGE_LAYERS, large_cases, large_n
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -144,19 +144,75 @@ def test_formats(ng, obs_dtype, grad_dtype):
     judged(out, [[sides[0]], [sides[1]]], params, "tanh", f"{obs_dtype} x {grad_dtype}")
 
 
-@pytest.mark.parametrize("n,K,H,O,small", [(65, 35, 64, 19, False), (65, 36, 128, 33, False), (33, 9, 32, 5, False), (0, 35, 64, 19, True)])
+def compute_units():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("n,K,H,O,small", [(65, 35, 64, 19, False), (65, 36, 128, 33, False), (33, 9, 32, 5, False), (0, 35, 64, 19, True),
+                                           (0, 35, 32, 19, True), (0, 35, 128, 19, True)])
 def test_exact_integer_pin(ng, n, K, H, O, small):
     """every intermediate and every partial sum is an exact float32: the result EQUALS the int64 one, units at z == 0
-    included.  The last case takes its n from the grid cap: every workgroup runs two passes and a part of a third."""
+    included.  The last cases take their n from the grid cap: every workgroup runs two passes and a part of a third."""
     if n == 0:
-        cap = torch.cuda.get_device_properties(0).multi_processor_count
+        cap = compute_units()
         n = 2 * cap * ng.rows_per_pass(H) + 65
+        print(f"{cap} compute units: n = {n}")
     x, params, d3, want = G.integer_case(n, K, H, O, small=small)
     for dtype in ("int32", "float32"):
         got = call(ng, [(x.astype(dtype), d3.astype(np.float32))], params, "relu", shared=False, obs_dtype=dtype)[0]
         for name, g, w in zip(G.NAMES, got, want):
             assert np.array_equal(g.astype(np.int64), w), (name, dtype)
     print(f"integer case n = {n}: equal")
+
+
+@pytest.mark.parametrize("shared", (False, True), ids=("two_nets", "shared_net"))
+def test_exact_integer_pin_two_agents_past_the_first_pass(ng, shared):
+    """H = 64 at the cap-sized n with both agents: on nets of their own each result EQUALS its own int64 one; on a shared net
+    the result EQUALS the int64 sum over the rows of both sides (one integer case of 2 n rows, cut in halves: its own
+    assertions keep every partial sum of the whole below 2^24)."""
+    K, H, O = 35, 64, 19
+    cap = compute_units()
+    n = 2 * cap * ng.rows_per_pass(H) + 65
+    print(f"{cap} compute units: n = {n} per agent")
+    f = lambda x, d3: (x.astype(np.int32), d3.astype(np.float32))  # noqa: E731
+    if shared:
+        x, params, d3, want = G.integer_case(2 * n, K, H, O, small=True)
+        got = call(ng, [f(x[:n], d3[:n]), f(x[n:], d3[n:])], params, "relu", shared=True, obs_dtype="int32")
+        wants = [want]
+    else:
+        cases = [G.integer_case(n, K, H, O, seed=seed, small=True) for seed in (5, 6)]
+        assert not np.array_equal(cases[0][1][0], cases[1][1][0])
+        got = call(ng, [f(c[0], c[2]) for c in cases], [c[1] for c in cases], "relu", shared=False, obs_dtype="int32")
+        wants = [c[3] for c in cases]
+    assert len(got) == len(wants)
+    for group, want in zip(got, wants):
+        for name, g, w in zip(G.NAMES, group, want):
+            assert np.array_equal(g.astype(np.int64), w), name
+    print(f"integer case n = {n}, two agents, {'a shared net' if shared else 'two nets'}: equal")
+
+
+@pytest.mark.parametrize("activation", N.ACTIVATIONS)
+@pytest.mark.parametrize("hidden", sorted(LARGE_LAYERS))
+def test_past_the_first_pass_under_the_documented_roundings(ng, hidden, activation):
+    """n = CUs * R + R + 33: workgroup 0 takes a second, whole pass, workgroup 1 a partial one, the others none.  One agent,
+    two nets and a shared net, judged with the header's own count of roundings -- (rows of a workgroup) + (workgroups - 1) +
+    (1 for a shared net) -- in the sums over the rows, not with n: under n a lost pass can stay inside the tolerance
+    (tests/test_netgrad_host.py shows both)."""
+    cus = compute_units()
+    n = large_n(hidden, cus)
+    print(f"{cus} compute units: n = {n}")
+    for what, sides, params, shared, groups in large_cases(hidden, activation, cus):
+        m = G.documented_roundings(n, hidden, cus, shared)
+        out = call(ng, sides, params, activation, shared=shared)
+        assert len(out) == len(groups)
+        worst = 0.0
+        for got, (own, own_params) in zip(out, groups):
+            refs, tols, ambiguous = G.judge(own, own_params, activation, roundings=m)
+            assert ambiguous == 0
+            share, beyond = G.worst_share(got, refs, tols)
+            assert not beyond, (what, share, beyond)
+            worst = max(worst, share)
+        print(f"H = {hidden} {activation} n = {n} {what}, {m} roundings: worst error / tolerance {worst:.4f}")
 
 
 def test_nan_containment(ng):

@@ -171,6 +171,10 @@ def test_forward_cases(lib, net_lib, index):
     members untouched, and a second call returns the same bits"""
     case = PJ.forward_cases()[index]
     K, H, O, P, n = case["K"], case["H"], case["O"], case["P"], case["n"]
+    if "max_cus" in case:  # (a case sized so that a workgroup walks several groups under the grid cap of such a device)
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        print(f"case {index}: {cus} compute units, n = {n}")
+        assert cus <= case["max_cus"], "this case's n is sized for a smaller grid cap: it no longer reaches the path it is here for"
     obs, params, members, sets, plans = case_setup(lib, case)
     kw = dict(obs_pitch=K + case["obs_extra"], out_pitch=O + case["out_extra"], offset=case["offset"])
     have = run_pool(lib, obs, case["obs_dtype"], sets, plans, case["activation"], case["out_dtype"], shape=(H, O), **kw)

@@ -287,6 +287,25 @@ def test_the_exact_integer_cases_are_exact_in_float32():
         assert len(np.unique(want)) > want.size // 4 and not np.array_equal(params[2], params[2].T)
 
 
+def test_the_integer_case_keeps_its_results_and_its_bounds_at_the_large_batch():
+    """integer_case's products are float64 BLAS calls, exact below 2^53 (asserted by exact_matmul): at the sizes above the result
+    is what numpy's int64 products give on the same draws; and its own bounds hold at the batch of
+    tests/test_gpu_net.py's large tests on 256 compute units"""
+    for n, K, H, O in ((65, 35, 64, 19), (65, 36, 128, 33), (33, 9, 32, 5)):
+        x, params, want = N.integer_case(n, K, H, O)
+        h = x
+        for layer in range(3):
+            h = h @ params[2 * layer].astype(np.int64).T + params[2 * layer + 1].astype(np.int64)
+            h = np.maximum(h, 0) if layer < 2 else h
+        assert x.dtype == want.dtype == np.int64 and np.array_equal(want, h), (n, K, H, O)
+    with pytest.raises(AssertionError):
+        N.exact_matmul(np.full((1, 2), 2 ** 27), np.full((2, 1), 2 ** 26))
+    n = 2 * (2 * 256) * 128 + 128 + 37
+    for K, H, O in ((35, 32, 19), (35, 64, 19), (72, 128, 40)):
+        x, params, want = N.integer_case(n, K, H, O)
+        assert want.shape == (n, O) and np.abs(want).max() > 0
+
+
 @pytest.mark.parametrize("activation", N.ACTIVATIONS)
 def test_actor_critic_forward_matches_the_judge_on_the_cpu(activation):
     import torch
