@@ -14,7 +14,10 @@ on ``ActorCritic.forward`` and torch autograd; ``--torch-optimizer`` (``native_o
 of the optimizer.  ``native_batch=True`` moves the data between these stages with ``batch.RolloutBuffer``: one ``store`` per
 policy step instead of eleven ``copy_`` calls, and one ``minibatch`` per minibatch instead of ``randperm`` and ten index
 gathers.  It is off by default, because what it costs against the torch route is not measured yet:
-``--native-batch`` turns it on.
+``--native-batch`` turns it on.  ``fused_act=True`` (``--fused-act``) makes the rollout's first two launches one:
+``ActorCritic.act_sample`` goes from the observations to action, log-prob, entropy and value (``act.sample``), returns the
+bits of the two launches and draws from the same stream, so the losses are the same numbers; it stores the head only on the
+``native_batch`` route, whose ``store`` takes it.  Off by default; which route is faster at which batch: README.
 """
 import argparse
 import sys
@@ -29,7 +32,7 @@ from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True, native_optimizer=True, native_batch=False):
+         native_update=True, native_optimizer=True, native_batch=False, fused_act=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -56,10 +59,17 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
     losses, policy_step = [], 0
 
     for it in range(iters):
-        # ---- rollout: k policy steps, three launches each (net, head, step) ------------------------------------------------
+        # ---- rollout: k policy steps, three launches each (net, head, step), two with fused_act ------------------------------
         for t in range(k):
-            head = model.act(obs, out=head)                       # {agent: [n, A + 1]}: logits and value
-            picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
+            if fused_act:                                         # one launch: the head only where the buffer stores it
+                picked = model.act_sample(obs, seed=seed, step=policy_step, head=native_batch, out=picked)
+                values = picked["values"]
+                if native_batch:
+                    head = picked["head"]
+            else:
+                head = model.act(obs, out=head)                   # {agent: [n, A + 1]}: logits and value
+                picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
+                values = {a: head[a][:, A] for a in agents}
             if native_batch:
                 if buf is None:
                     buf = batch.RolloutBuffer(k, n, dict(obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head),
@@ -72,7 +82,7 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
                     buf_obs[a][t].copy_(obs[a])
                     buf_act[a][t].copy_(picked["actions"][a])
                     buf_logp[a][t].copy_(picked["log_probs"][a])
-                    buf_val[a][t].copy_(head[a][:, A])
+                    buf_val[a][t].copy_(values[a])
             obs, rewards, terminations, _, _ = env.step(picked["actions"])
             if not native_batch:
                 for a in agents:
@@ -133,6 +143,7 @@ if __name__ == "__main__":
     p.add_argument("--torch-update", action="store_true", help="update through ActorCritic.forward and torch autograd")
     p.add_argument("--torch-optimizer", action="store_true", help="clip_grad_norm_ and torch.optim.Adam instead of optim.Adam")
     p.add_argument("--native-batch", action="store_true", help="batch.RolloutBuffer: one store per policy step, one gather per minibatch")
+    p.add_argument("--fused-act", action="store_true", help="ActorCritic.act_sample: the net's forward and the sampling in one launch")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
-         native_optimizer=not args.torch_optimizer, native_batch=args.native_batch)
+         native_optimizer=not args.torch_optimizer, native_batch=args.native_batch, fused_act=args.fused_act)

@@ -2,6 +2,8 @@
 // one parameter set into LDS in operand order, the three layers of one tile of 32 batch rows, and what the two entry points
 // check and size alike.  include/pikazoo_pool.h promises pz_mlp_forward's bits for every row: both kernels call tile_forward,
 // so the k order, the operand permutation and the roundings are written down here and nowhere else.
+// libpikazoo_act.so (pz_act.hip) shares the staging, the dense layer and the checks, and takes the layers without the store
+// from tile_layers, below tile_forward.
 //
 // Every layer is computed as W . X^T on v_mfma_f32_32x32x2_f32 (exact float32: a k-ordered chain of fused multiply-adds):
 // the weights are the A operand, a tile of 32 batch rows the B operand, so an accumulator tile has its hidden index in the
@@ -263,6 +265,89 @@ __device__ __forceinline__ void tile_forward(const Staged& s, const void* obs, v
             for (int r = 0; r < 16; ++r) {
                 const int o = 32 * t + acc_row(r, half);
                 if (o < O) store_out(out, out_format, out_at + o, y[t][r]);
+            }
+    }
+}
+
+// tile_forward's three layers ONCE MORE, without the store, for libpikazoo_act.so (pz_act.hip), which goes on from the head in
+// registers: output o = 32 t + acc_row(r, half) of the lane's row comes back as y[t][r].  It stands beside tile_forward rather
+// than under it because a tile_forward that called it compiled pz_net.hip's and pz_pool.hip's kernels to other instruction
+// streams (the same arithmetic, scheduled differently), and those kernels keep theirs.  The two texts must stay
+// line for line alike from load_chunk to the layer-3 dense: include/pikazoo_act.h promises pz_mlp_forward's bits, and
+// tests/test_gpu_act.py holds the two to each other.
+template <int H, int ACT>
+__device__ __forceinline__ void tile_layers(const Staged& s, const void* obs, int64_t row, bool live, int K, int O, int64_t obs_pitch,
+                                            int obs_format, int lane, f32x16 (&y)[2])
+{
+    constexpr int TH = H / 32;
+    const int half = lane >> 5, K8 = k8_of(K), TO = out_tiles_of(O);
+    const float* lds1 = s.w1;
+    const int chunks = K8 / (2 * kChunk);
+    const int64_t obs_at = row * obs_pitch;
+    auto load_chunk = [&](int c, float (&x)[kChunk]) {
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) {
+            const int k = 2 * (kChunk * c + j) + half;
+            x[j] = live && k < K ? load_obs(obs, obs_format, obs_at + k) : 0.0f;
+        }
+    };
+    auto load_weights = [&](int c, float (&w)[kChunk * TH]) {
+#pragma unroll
+        for (int e = 0; e < kChunk * TH; ++e) w[e] = lds1[(c * kChunk * TH + e) * 64 + lane];
+    };
+    float x[kChunk], xn[kChunk] = {}, w[kChunk * TH], wn[kChunk * TH] = {};
+    load_chunk(0, x);
+    load_weights(0, w);
+
+    f32x16 h1[TH];
+#pragma unroll
+    for (int t = 0; t < TH; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h1[t][r] = s.b1[32 * t + acc_row(r, half)];
+    for (int c = 0; c < chunks; ++c) {
+        if (c + 1 < chunks) {
+            load_chunk(c + 1, xn);
+            load_weights(c + 1, wn);
+        }
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j)
+#pragma unroll
+            for (int t = 0; t < TH; ++t) h1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j * TH + t], x[j], h1[t], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) x[j] = xn[j];
+#pragma unroll
+        for (int e = 0; e < kChunk * TH; ++e) w[e] = wn[e];
+    }
+#pragma unroll
+    for (int t = 0; t < TH; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h1[t][r] = activate<ACT>(h1[t][r]);
+
+    f32x16 h2[TH];
+    dense<TH, TH, TH>(h1, s.w2, s.b2, h2, lane);
+#pragma unroll
+    for (int t = 0; t < TH; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h2[t][r] = activate<ACT>(h2[t][r]);
+
+    if (TO == 1)
+        dense<TH, 1, 2>(h2, s.w3, s.b3, y, lane);
+    else
+        dense<TH, 2, 2>(h2, s.w3, s.b3, y, lane);
+}
+
+// a live lane's share of its float32 row, from tile_layers' accumulators: what tile_forward stores at PZ_NET_OUT_FLOAT32
+__device__ __forceinline__ void store_tile_float32(const f32x16 (&y)[2], float* out, int64_t row, bool live, int O, int64_t out_pitch, int lane)
+{
+    const int half = lane >> 5;
+    if (live) {
+        const int64_t out_at = row * out_pitch;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = 32 * t + acc_row(r, half);
+                if (o < O) out[out_at + o] = y[t][r];
             }
     }
 }

@@ -60,25 +60,7 @@ __device__ __forceinline__ void finish(const Common& c, int side, int64_t g, con
     if (c.ent[side]) c.ent[side][g] = s.bad ? nan : s.H;
 }
 
-// Philox4x32-10 (Salmon et al., SC'11)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& o0,
-                                              uint32_t& o1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        c0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        c1 = (uint32_t)p1;
-        c2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o0 = c0;
-    o1 = c1;
-}
-
+// (philox4x32_10: pz_policy_rows.hpp, shared with pz_act.hip)
 template <int LF>
 __global__ void __launch_bounds__(kLanes) sample_kernel(const SampleArgs a)
 {
@@ -93,12 +75,9 @@ __global__ void __launch_bounds__(kLanes) sample_kernel(const SampleArgs a)
     const int64_t g = g0 + lane;
     const float* row = image + lane * stride;
     const RowStats s = row_stats(row, c.A);
-    // step 3: the draw
+    // step 3: the draw (pz_policy_rows.hpp)
     const uint64_t T = a.step + (a.step_dev ? *a.step_dev : 0);
-    const uint64_t G = (uint64_t)(a.first_game + g);
-    uint32_t w0, w1;
-    philox4x32_10((uint32_t)G, (uint32_t)(G >> 32), (uint32_t)T, 2u + 4u * (uint32_t)(T >> 32), a.key0, a.key1, w0, w1);
-    const float u = (float)((side ? w1 : w0) >> 8) * 0x1p-24f;
+    const float u = draw_uniform((uint64_t)(a.first_game + g), T, a.key0, a.key1, side);
     // step 4: the same sums again (the same expf of the same arguments: the same c_i), counted against the threshold
     const float thr = u * s.S;
     float cum = 0.0f;

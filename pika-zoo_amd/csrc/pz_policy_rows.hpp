@@ -1,7 +1,8 @@
-// The logit rows of the categorical head, shared by the translation units that read them (pz_policy.hip, pz_ppo.hip): the
-// element formats, a wave's span staged into its transposed LDS image, the row statistics every kernel of either library
-// runs as this one text (the log-prob and entropy bits two launches must share come from here), the action read, and the
-// dense store of a gradient image.  pz_policy.hip describes the layout and why it is what it is.
+// The logit rows of the categorical head, shared by the translation units that read them (pz_policy.hip, pz_ppo.hip,
+// pz_act.hip): the element formats, a wave's span staged into its transposed LDS image, the row statistics every kernel of
+// these libraries runs as this one text (the log-prob and entropy bits two launches must share come from here), the Philox
+// block and the uniform draw (pz_sample_actions' and pz_mlp_act's alike), steps 4 and 5 as pz_act.hip runs them, the action
+// read, and the dense store of a gradient image.  pz_policy.hip describes the layout and why it is what it is.
 #ifndef PZ_POLICY_ROWS_HPP
 #define PZ_POLICY_ROWS_HPP
 #include <hip/hip_runtime.h>
@@ -170,6 +171,59 @@ __device__ __forceinline__ RowStats row_stats(const float* row, int A)
     s.m = m, s.S = c, s.logS = logf(c), s.last = last, s.bad = bad;
     s.H = s.logS - t / c;
     return s;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t& o0,
+                                              uint32_t& o1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        c0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        c1 = (uint32_t)p1;
+        c2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o0 = c0;
+    o1 = c1;
+}
+
+// step 3: the uniform draw of global game G at step T for agent `side`
+__device__ __forceinline__ float draw_uniform(uint64_t G, uint64_t T, uint32_t key0, uint32_t key1, int side)
+{
+    uint32_t w0, w1;
+    philox4x32_10((uint32_t)G, (uint32_t)(G >> 32), (uint32_t)T, 2u + 4u * (uint32_t)(T >> 32), key0, key1, w0, w1);
+    return (float)((side ? w1 : w0) >> 8) * 0x1p-24f;
+}
+
+// Steps 4 and 5 as pz_act.hip runs them: sample_kernel's and finish's own lines of pz_policy.hip once more.  Those two keep
+// their text where it is, because calling these functions from them moved their kernels' instruction streams (DESIGN.md
+// 4.23); the expressions must stay alike, and tests/test_gpu_act.py holds the two launches to each other bit for bit.
+// step 4: the same sums again (the same expf of the same arguments: the same c_i), counted against the threshold
+__device__ __forceinline__ int draw_action(const float* row, int A, const RowStats& s, float u)
+{
+    const float thr = u * s.S;
+    float cum = 0.0f;
+    int act = 0;
+    for (int i = 0; i < A - 1; ++i) {
+        cum += expf(row[i] - s.m);
+        act += cum <= thr;
+    }
+    return s.bad ? 0 : min(act, s.last);
+}
+
+// step 5's log-prob of action a (NaN for a row of step 6 or an action outside [0, A))
+__device__ __forceinline__ float action_log_prob(const float* row, int A, const RowStats& s, int a)
+{
+    const bool in_range = (unsigned)a < (unsigned)A;
+    const float la = row[in_range ? a : 0];
+    const float nan = __uint_as_float(0x7FC00000u);
+    const float logp = (la - s.m) - s.logS;
+    return (s.bad || !in_range) ? nan : logp;
 }
 
 __device__ __forceinline__ int load_action(const void* act, int format, int64_t g)

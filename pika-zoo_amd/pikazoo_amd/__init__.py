@@ -29,16 +29,19 @@
 
     from pikazoo_amd import league                     # league matchmaking: per-member results and weighted draws, one launch each
     table = league.tally(terminations, env.scores, members, 8); members = league.draw(league.pfsp_weights(table, 8), n, seed=0)
+
+    from pikazoo_amd import act                        # net forward + action sampling: observations -> action, log-prob, entropy, value
+    out = model.act_sample(obs, seed=7, step=env.steps_done)      # one launch; the bits of model.act + policy.sample
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

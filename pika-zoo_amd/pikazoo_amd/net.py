@@ -188,7 +188,8 @@ class ActorCritic(torch.nn.Module):
     with the gains sqrt 2, sqrt 2 and 0.01, biases 0.
 
     ``forward(obs)`` is the torch route, differentiable.  ``act(obs)`` is :func:`forward` of this module (one launch, no
-    graph): the rollout side.  ``evaluate(obs)`` is the same launch made differentiable by ``netgrad.head``: the update side,
+    graph): the rollout side; ``act_sample(obs, seed, step)`` is that launch and ``policy.sample`` on its logits in one
+    (``act.sample``).  ``evaluate(obs)`` is the same launch made differentiable by ``netgrad.head``: the update side,
     one call forward and one call backward for both agents.  All read the same storage, so there is nothing to synchronise
     after ``optimizer.step()``."""
 
@@ -224,6 +225,16 @@ class ActorCritic(torch.nn.Module):
         this module's parameters, in one launch"""
         with torch.no_grad():
             return forward(obs, self.parameter_tensors(), self.activation, out=out, out_dtype=out_dtype)
+
+    def act_sample(self, obs, seed: int, step=0, first_game: int = 0, head: bool = False, out=None):
+        """:meth:`act` and ``policy.sample`` on its logits in ONE launch (``act.sample``, imported on first use: nothing loads
+        libpikazoo_act.so before): ``{"actions", "log_probs", "entropy", "values"}`` of a tensor or an ``{agent: tensor}`` dict
+        of observations, plus ``"head"`` when asked -- the bits of the two calls, from the same Philox stream"""
+        from . import act
+
+        with torch.no_grad():
+            return act.sample(obs, self.parameter_tensors(), self.num_actions, seed, step=step, first_game=first_game,
+                              activation=self.activation, head=head, out=out)
 
     def evaluate(self, obs):
         """the ``[N, num_actions + 1]`` float32 head of a tensor or an ``{agent: tensor}`` dict of observations, as
