@@ -18,6 +18,10 @@ self-play -- members the learner loses to more often -- once per iteration (``re
 plan), pushes the snapshots through it so that an overwritten slot does not inherit results, and the log shows the learner's
 win rate against each member.  Without the flag the opponents are drawn uniformly with ``torch.randint`` and nobody keeps
 score: the loop launches what it launched before the flag existed.
+
+``--fused-act`` makes the policy step TWO launches instead of three: ``pool.Snapshots.act_sample`` (``pikazoo_amd.pool_act``:
+the net over the pool and the draw in one launch, the learner's log-probabilities and values only, the opponents' side its
+actions alone) -> ``env.step``.  It returns the bits of the two launches it replaces, so the losses are the same floats.
 """
 import argparse
 import sys
@@ -33,7 +37,7 @@ from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print, pool_size=8,
-         snapshot_every=2, pfsp=False):
+         snapshot_every=2, pfsp=False, fused_act=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
     env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
@@ -68,14 +72,19 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
             plan = plans[len(league)] = pool.plan(members, len(league), out=plans.get(len(league)))
         sides = {learner: None, opponent: plan}                   # the learner's side needs no plan: member 0 everywhere
 
-        # ---- rollout: k policy steps, three launches each (net over the pool, head, step) ---------------------------------
+        # ---- rollout: k policy steps, three launches each (net over the pool, head, step), two with fused_act -------------
         for t in range(k):
-            head = league.act(obs, sides, out=head)               # {agent: [n, A + 1]}: each row under its own member
-            picked = policy.sample({a: head[a][:, :A] for a in env.agents}, seed=seed, step=policy_step, out=picked)
+            if fused_act:                                         # the learner's statistics only: the update reads no others
+                picked = league.act_sample(obs, sides, seed=seed, step=policy_step, stats={learner}, out=picked)
+                values = picked["values"][learner]
+            else:
+                head = league.act(obs, sides, out=head)           # {agent: [n, A + 1]}: each row under its own member
+                picked = policy.sample({a: head[a][:, :A] for a in env.agents}, seed=seed, step=policy_step, out=picked)
+                values = head[learner][:, A]
             buf_obs[t].copy_(obs[learner])
             buf_act[t].copy_(picked["actions"][learner])
             buf_logp[t].copy_(picked["log_probs"][learner])
-            buf_val[t].copy_(head[learner][:, A])
+            buf_val[t].copy_(values)
             obs, rewards, terminations, _, _ = env.step(picked["actions"])
             if pfsp:
                 matchmaker.record(terminations[learner], env.scores)   # the terminal frame's scores: the reset comes with the next step
@@ -120,5 +129,7 @@ if __name__ == "__main__":
     p.add_argument("--pool", type=int, default=8, help="pool members: the learner and pool - 1 snapshots (at most 16)")
     p.add_argument("--snapshot-every", type=int, default=2, help="iterations between two snapshots of the learner")
     p.add_argument("--pfsp", action="store_true", help="a league: record results per member and draw opponents by prioritised fictitious self-play")
+    p.add_argument("--fused-act", action="store_true", help="the net over the pool and the action draw in one launch (pikazoo_amd.pool_act)")
     args = p.parse_args()
-    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every, pfsp=args.pfsp)
+    main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every, pfsp=args.pfsp,
+         fused_act=args.fused_act)

@@ -1,6 +1,6 @@
 """Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so, libpikazoo_learn.so, libpikazoo_policy.so,
 libpikazoo_ppo.so, libpikazoo_net.so, libpikazoo_netgrad.so, libpikazoo_optim.so, libpikazoo_batch.so, libpikazoo_pool.so,
-libpikazoo_league.so and libpikazoo_act.so -- for gfx950 with hipcc (in-tree, no JIT cache).
+libpikazoo_league.so, libpikazoo_act.so and libpikazoo_pool_act.so -- for gfx950 with hipcc (in-tree, no JIT cache).
 
     python pika-zoo_amd/build.py [--force]
 
@@ -19,8 +19,9 @@ a fifth, bound by pikazoo_amd/ppo.py, which shares csrc/pz_policy_rows.hpp with 
 (include/pikazoo_pool.h: pz_pool_plan, pz_mlp_forward_pool) a tenth, bound by pikazoo_amd/pool.py, which shares its tile
 code (csrc/pz_mlp_tile.hpp) with the sixth; the league library (include/pikazoo_league.h: pz_league_tally, pz_league_draw) an
 eleventh, bound by pikazoo_amd/league.py; the act library (include/pikazoo_act.h: pz_mlp_act) a twelfth, bound by
-pikazoo_amd/act.py, which shares csrc/pz_mlp_tile.hpp with the sixth and csrc/pz_policy_rows.hpp with the fourth.  The twelve
-compiles are independent and run side by side.
+pikazoo_amd/act.py, which shares csrc/pz_mlp_tile.hpp with the sixth and csrc/pz_policy_rows.hpp with the fourth; the pool-act library
+(include/pikazoo_pool_act.h: pz_mlp_act_pool) a thirteenth, bound by pikazoo_amd/pool_act.py, which shares both headers with the
+twelfth.  The thirteen compiles are independent and run side by side.
 """
 from __future__ import annotations
 
@@ -48,6 +49,7 @@ BATCH_LIB = LIB_DIR / "libpikazoo_batch.so"
 POOL_LIB = LIB_DIR / "libpikazoo_pool.so"
 LEAGUE_LIB = LIB_DIR / "libpikazoo_league.so"
 ACT_LIB = LIB_DIR / "libpikazoo_act.so"
+POOL_ACT_LIB = LIB_DIR / "libpikazoo_pool_act.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
 LEARN_SOURCES = [CSRC / "pz_learn.hip"]
@@ -60,17 +62,19 @@ BATCH_SOURCES = [CSRC / "pz_batch.hip"]
 POOL_SOURCES = [CSRC / "pz_pool.hip"]
 LEAGUE_SOURCES = [CSRC / "pz_league.hip"]
 ACT_SOURCES = [CSRC / "pz_act.hip"]
+POOL_ACT_SOURCES = [CSRC / "pz_pool_act.hip"]
 # every library with the translation units it is compiled from
 TARGETS = ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES), (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES),
            (NET_LIB, NET_SOURCES), (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES),
            (POOL_LIB, POOL_SOURCES), (LEAGUE_LIB, LEAGUE_SOURCES))
 # ... and the libraries added since (TARGETS keeps its eleven entries): what build() and needs_build() walk
-ALL_TARGETS = TARGETS + ((ACT_LIB, ACT_SOURCES),)
+ALL_TARGETS = TARGETS + ((ACT_LIB, ACT_SOURCES), (POOL_ACT_LIB, POOL_ACT_SOURCES))
 DEPS = [source for _, sources in ALL_TARGETS for source in sources] + [
     CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
     CSRC / "pz_policy_rows.hpp", CSRC / "pz_mlp_tile.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
     INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h",
-    INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h", INCLUDE / "pikazoo_league.h", INCLUDE / "pikazoo_act.h"]
+    INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h", INCLUDE / "pikazoo_league.h", INCLUDE / "pikazoo_act.h",
+    INCLUDE / "pikazoo_pool_act.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
@@ -129,9 +133,9 @@ def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
     """The product library (returned) with the diagnostics, the learning, the policy, the PPO, the net, the net-gradient, the
-    optimizer, the batch, the pool, the league and the act library beside it: each is compiled when it is missing or stale,
+    optimizer, the batch, the pool, the league, the act and the pool-act library beside it: each is compiled when it is missing or stale,
     the compiles side by side (a cold build takes about as long as the product library alone: some three minutes; an
-    up-to-date tree costs twelve file reads)."""
+    up-to-date tree costs thirteen file reads)."""
     if any("PZ_DIAGNOSTIC_BUILD" in f for f in extra_flags):
         # csrc/pz_diagnostic.hpp: the one compile-time switch of the kernels -- tools/ab.py builds such variants into
         # tools/bin/; the product path never holds one (and _native.load() would refuse its build id "diagnostic")

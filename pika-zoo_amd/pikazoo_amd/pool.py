@@ -8,6 +8,7 @@ through the parameter set of its own pool member.
     members = torch.randint(len(league), (n,), device="cuda")   # each game draws its opponent
     plan = pool.plan(members, len(league))                      # rows grouped by member: once per re-assignment
     head = league.act(obs, {"player_1": None, "player_2": plan})    # one launch per policy step, both agents
+    out = league.act_sample(obs, {"player_1": None, "player_2": plan}, seed=7, step=t, stats={"player_1"})   # ... with the draw
 
     pool.forward(obs, member_params, plans)                     # the same launch on any P parameter sets
 
@@ -251,3 +252,15 @@ class Snapshots:
         :meth:`member_params` (plans are made for ``len(self)`` members)"""
         with torch.no_grad():
             return forward(obs, self.member_params(), plans, self.model.activation, out=out, out_dtype=out_dtype)
+
+    def act_sample(self, obs, plans, seed: int, step=0, first_game: int = 0, stats=None, head=False, out=None):
+        """:meth:`act` and ``policy.sample`` on its logits in ONE launch (``pool_act.sample``, imported on first use: nothing
+        loads libpikazoo_pool_act.so before): ``{"actions", "log_probs", "entropy", "values"}``, every row under its own
+        member, the bits of the two calls from the same Philox stream.  ``stats``: the agents whose log-probabilities,
+        entropies and values are wanted (``None``: all; a league passes the learner alone); ``head``: those that also get the
+        ``[N, num_actions + 1]`` head"""
+        from . import pool_act
+
+        with torch.no_grad():
+            return pool_act.sample(obs, self.member_params(), plans, self.model.num_actions, seed, step=step, first_game=first_game,
+                                   activation=self.model.activation, stats=stats, head=head, out=out)
