@@ -22,6 +22,12 @@ score: the loop launches what it launched before the flag existed.
 ``--fused-act`` makes the policy step TWO launches instead of three: ``pool.Snapshots.act_sample`` (``pikazoo_amd.pool_act``:
 the net over the pool and the draw in one launch, the learner's log-probabilities and values only, the opponents' side its
 actions alone) -> ``env.step``.  It returns the bits of the two launches it replaces, so the losses are the same floats.
+
+``--egocentric`` makes the interface side-symmetric: ``EgocentricObservation(NormalizeObservation(SimplifyAction(env)))``.  The
+snapshots are copies of a net that only ever played ``player_1``; as ``player_2`` they otherwise sit on rows they were never
+trained on, with left and right reversed.  With the flag ``player_2``'s rows are what ``player_1`` would see in the mirrored
+game (``pikazoo_amd.ego``, one launch behind the step) and the 13 relative actions mean the same on both sides.  Whether that
+trains better is what the flag is there to find out; without it nothing changes.
 """
 import argparse
 import sys
@@ -33,14 +39,16 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
 from pikazoo_amd import league as matchmaking  # noqa: E402
 from pikazoo_amd import learn, net, optim, pikazoo_v0, policy, pool, ppo  # noqa: E402
-from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
+from pikazoo_amd.wrappers import EgocentricObservation, NormalizeObservation, SimplifyAction  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print, pool_size=8,
-         snapshot_every=2, pfsp=False, fused_act=False):
+         snapshot_every=2, pfsp=False, fused_act=False, egocentric=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
-    env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
+    env = pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False)
+    # egocentric: relative actions and player_2's rows mirrored -- both sides are ONE task for a net
+    env = EgocentricObservation(NormalizeObservation(SimplifyAction(env))) if egocentric else NormalizeObservation(env)
     learner, opponent = env.agents
     A = env.action_space(learner).n
     obs, _ = env.reset()
@@ -130,6 +138,7 @@ if __name__ == "__main__":
     p.add_argument("--snapshot-every", type=int, default=2, help="iterations between two snapshots of the learner")
     p.add_argument("--pfsp", action="store_true", help="a league: record results per member and draw opponents by prioritised fictitious self-play")
     p.add_argument("--fused-act", action="store_true", help="the net over the pool and the action draw in one launch (pikazoo_amd.pool_act)")
+    p.add_argument("--egocentric", action="store_true", help="relative actions and player_2's rows mirrored: one net, either side")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, pool_size=args.pool, snapshot_every=args.snapshot_every, pfsp=args.pfsp,
-         fused_act=args.fused_act)
+         fused_act=args.fused_act, egocentric=args.egocentric)

@@ -18,6 +18,9 @@ gathers.  It is off by default, because what it costs against the torch route is
 ``ActorCritic.act_sample`` goes from the observations to action, log-prob, entropy and value (``act.sample``), returns the
 bits of the two launches and draws from the same stream, so the losses are the same numbers; it stores the head only on the
 ``native_batch`` route, whose ``store`` takes it.  Off by default; which route is faster at which batch: README.
+``egocentric=True`` (``--egocentric``) makes the env ``EgocentricObservation(NormalizeObservation(SimplifyAction(env)))``:
+``player_2``'s rows are what ``player_1`` would see in the mirrored game and the 13 relative actions mean the same on both
+sides, so the shared weights learn one task instead of two.  Whether that trains better is what the flag is there to find out.
 """
 import argparse
 import sys
@@ -28,14 +31,16 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
 from pikazoo_amd import batch, learn, net, optim, pikazoo_v0, policy, ppo  # noqa: E402
-from pikazoo_amd.wrappers import NormalizeObservation  # noqa: E402
+from pikazoo_amd.wrappers import EgocentricObservation, NormalizeObservation, SimplifyAction  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True, native_optimizer=True, native_batch=False, fused_act=False):
+         native_update=True, native_optimizer=True, native_batch=False, fused_act=False, egocentric=False):
     """Returns the loss of every minibatch update, as floats."""
     torch.manual_seed(seed)
-    env = NormalizeObservation(pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False))
+    env = pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False)
+    # egocentric: relative actions and player_2's rows mirrored -- both sides are ONE task for a net
+    env = EgocentricObservation(NormalizeObservation(SimplifyAction(env))) if egocentric else NormalizeObservation(env)
     agents = env.agents
     A = env.action_space(agents[0]).n
     obs, _ = env.reset()
@@ -144,6 +149,8 @@ if __name__ == "__main__":
     p.add_argument("--torch-optimizer", action="store_true", help="clip_grad_norm_ and torch.optim.Adam instead of optim.Adam")
     p.add_argument("--native-batch", action="store_true", help="batch.RolloutBuffer: one store per policy step, one gather per minibatch")
     p.add_argument("--fused-act", action="store_true", help="ActorCritic.act_sample: the net's forward and the sampling in one launch")
+    p.add_argument("--egocentric", action="store_true", help="relative actions and player_2's rows mirrored: one net, either side")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
-         native_optimizer=not args.torch_optimizer, native_batch=args.native_batch, fused_act=args.fused_act)
+         native_optimizer=not args.torch_optimizer, native_batch=args.native_batch, fused_act=args.fused_act,
+         egocentric=args.egocentric)

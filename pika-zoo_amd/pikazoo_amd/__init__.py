@@ -35,16 +35,19 @@
 
     from pikazoo_amd import pool_act                   # the same over a pool: each row its own member's net, then the draw
     out = snapshots.act_sample(obs, plans, seed=7, step=env.steps_done, stats={"player_1"})   # one launch; pool.forward + policy.sample
+
+    from pikazoo_amd import ego                        # egocentric rows: player_2 sees the court as player_1 does, one launch
+    ego.mirror(obs["player_2"], out=buf_obs[t])        # (wrappers.EgocentricObservation does it behind reset and step)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` / `pikazoo_amd.ego` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego"):
         import importlib
 
         return importlib.import_module("." + name, __name__)
