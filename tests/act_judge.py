@@ -45,6 +45,17 @@ def case_inputs(n, K, H, O, obs_dtype="float32", seed=0):
     return ([N.make_obs(n, K, obs_dtype, 10 * seed + 3 + s) for s in (0, 1)], [N.make_params(K, H, O, 10 * seed + 1 + s) for s in (0, 1)])
 
 
+# the case of tests/test_gpu_wide_pitch.py: 40 rows 2^31 elements apart, float16 observations, two agents on nets of their own.
+# CAP(40) is one row, and a cap is a condition, not a measurement: the draw and the seed are picked so that the float32
+# restatement has NO ambiguous row for either agent (tests/test_act_host.py asserts it and prints the shares)
+WIDE_CASE = dict(n=40, size=SIZES[0], activation="tanh", obs_dtype="float16", draw=1, seed=7)
+
+
+def wide_case_inputs():
+    K, H, O, _ = WIDE_CASE["size"]
+    return case_inputs(WIDE_CASE["n"], K, H, O, WIDE_CASE["obs_dtype"], seed=WIDE_CASE["seed"])
+
+
 def uniforms(draw, n):
     seed, first_game, step, step_dev = draw
     return J.uniforms(seed, first_game, step, step_dev, n)

@@ -2,6 +2,12 @@
 involution ``PI`` of the 18 actions, the mutants of the definition that the tests must tell from it, and the case lists of the
 GPU test (tests/test_gpu_ego.py), which the host test (tests/test_ego_host.py) plays the mutants on.
 
+Two case tables.  ``row_cases()`` holds what a launch can get wrong within ONE trip of the kernels' grid-stride loops: its
+largest case is 257 rows, 8 995 elements, and a thread takes a second trip only above 524 288.  ``LARGE_CASES`` (and
+``LARGE_ACTION_COUNT``) are about 2.5 strides each, so that the advance of the column, the (row, column) walk with its carry
+and the stride itself run; ``mirror_elements`` and ``walked_buffer`` say what a walk that holds wrong columns, or does
+elements twice or not at all, would leave.
+
 Rows are numpy arrays ``[..., 35]`` in the storage type of their format: int32 (0), float32 (1), int16 (2), float16 (3, 5) and,
 numpy having no bfloat16, uint16 holding the bfloat16 bits (4, 6).  bfloat16 is done in uint16 / uint32 bit arithmetic with
 round to nearest even."""
@@ -182,31 +188,153 @@ def _sentinel(count, fmt):
     return np.full(count, word, bits(np.zeros(1, STORAGE[fmt])).dtype)
 
 
+def _rows_of(buffer, at, rows, pitch):
+    """the [rows, pitch] view of a buffer's rows from element `at` (every buffer ends GUARD elements behind rows * pitch)"""
+    return buffer[at:at + rows * pitch].reshape(rows, pitch)
+
+
+def case_rows(case):
+    """the rows of a case in their storage type (a large case: shared and read-only, see :func:`large_rows`)"""
+    if case.get("large"):
+        return large_rows(case["fmt"], case["rows"], case["seed"])[0]
+    return encode(content(case["rows"], case["seed"]), case["fmt"])
+
+
 def case_buffers(case):
     """(input buffer, output buffer or None when in place, the rows) as unsigned words: sentinels everywhere but in the rows'
     35 columns of the input"""
     fmt, rows = case["fmt"], case["rows"]
-    stored = encode(content(rows, case["seed"]), fmt)
+    stored = case_rows(case)
     src = _sentinel(GUARD + case["in_offset"] + rows * case["in_pitch"] + GUARD, fmt)
-    at = GUARD + case["in_offset"]
-    for r in range(rows):
-        src[at + r * case["in_pitch"]:at + r * case["in_pitch"] + DIM] = bits(stored[r])
+    _rows_of(src, GUARD + case["in_offset"], rows, case["in_pitch"])[:, :DIM] = bits(stored)
     dst = None if case["inplace"] else _sentinel(GUARD + case["out_offset"] + rows * case["out_pitch"] + GUARD, fmt)
     return src, dst, stored
 
 
-def expected_buffer(case, mutant=None):
+def expected_buffer(case, mutant=None, buffers=None):
     """the output buffer (the input buffer, in place) after the call: the judge's rows in the 35 columns, everything else as it
-    was"""
-    src, dst, stored = case_buffers(case)
-    want = mirror(stored, case["fmt"], None if mutant == "padding written" else mutant)
-    out = src.copy() if dst is None else dst
+    was; `buffers`: what :func:`case_buffers` returned for the case, where the caller holds it already (it is not written)"""
+    src, dst, stored = case_buffers(case) if buffers is None else buffers
+    if case.get("large") and mutant in (None, "padding written"):
+        want = large_rows(case["fmt"], case["rows"], case["seed"])[1]
+    else:
+        want = mirror(stored, case["fmt"], None if mutant == "padding written" else mutant)
+    out = src.copy() if dst is None else dst.copy()
     pitch = case["in_pitch"] if dst is None else case["out_pitch"]
-    at = GUARD + (case["in_offset"] if dst is None else case["out_offset"])
-    for r in range(case["rows"]):
-        out[at + r * pitch:at + r * pitch + DIM] = bits(want[r])
-        if mutant == "padding written" and r + 1 < case["rows"]:
-            out[at + r * pitch + DIM:at + (r + 1) * pitch] = 0
+    view = _rows_of(out, GUARD + (case["in_offset"] if dst is None else case["out_offset"]), case["rows"], pitch)
+    view[:, :DIM] = bits(want)
+    if mutant == "padding written":
+        view[:-1, DIM:] = 0
+    return out
+
+
+# ---- the cases past one grid stride ----------------------------------------------------------------------------------------------
+# pz_ego.hip caps a launch at 2 048 workgroups of 256 threads and strides: a thread takes a second trip of its loop only above
+# 524 288 elements (element by element) or 524 288 16-byte pieces (flat).  No case above comes near (257 rows are 8 995
+# elements), so the advance of the column, the (row, column) walk with its carry and the stride itself run in no case of
+# row_cases().  These do: about 2.5 strides each, so every thread takes two trips and about half of them a third
+# (tests/test_ego_host.py proves that on a numpy model of the three walks, with the cap read from the source).
+# by path; the flat path by the format's element size (150 003 and not 150 001: behind a head of 3 elements the latter's rest
+# is a whole number of 16-byte pieces, and the layout that is one element in would have no tail)
+LARGE_ROWS = {"pitched": 37501, 4: 150003, 2: 300001}
+LARGE_FLAT = (
+    (35, 35, 0, 0, False), (35, 35, 0, 0, True),          # aligned
+    (35, 35, 1, 1, False),                                # one element in: a head of 3 or 7 elements, the column starts from it
+    (35, 35, 35, 35, True),                               # a view from row 1
+)
+LARGE_PITCHED = (
+    (35, 35, 1, 0, False),                                # back to back, bases of different phase
+    (36, 35, 0, 0, False), (35, 40, 0, 0, False),
+    (40, 40, 1, 1, True), (36, 36, 0, 0, True),           # in place: the only calls in which an element done twice can show
+)
+LARGE_ACTION_COUNT = 1312537                              # odd; about 2.5 strides of one element
+
+
+def large_content(rows, seed):
+    """:func:`content` without its loop over the rows: by turns a row at the low bounds, at the high bounds, at random and at a
+    value of its own per column -- and no court column of the last two kinds at 216, the value the mirror leaves where it is
+    (432 - 216; in the normalised formats c_j - s = s there too), so that a mirror done in the wrong column or not at all shows"""
+    rng = np.random.default_rng([rows, seed, 1])
+    r = np.arange(rows)[:, None]
+    kind = (r + seed) % 4
+    own = LOW + (np.arange(DIM)[None, :] * 7 + 3 + r) % (HIGH - LOW + 1)
+    out = np.where(kind == 0, LOW, np.where(kind == 1, HIGH, np.where(kind == 2, rng.integers(LOW, HIGH + 1, (rows, DIM)), own)))
+    court = list(COURT)
+    out[:, court] = np.where(out[:, court] == WIDTH // 2, WIDTH // 2 + 1, out[:, court])
+    return out
+
+
+_large, _large_values = {}, {}
+
+
+def large_rows(fmt, rows, seed):
+    """(the rows of a large case in format `fmt`, the judge's mirror of them): computed once per (format, rows, seed), shared by
+    the cases and the tests that need them, read-only; the rows of one (format, rows) are held at a time"""
+    key = (fmt, rows, seed)
+    if key not in _large:
+        _large.clear()
+        if (rows, seed) not in _large_values:            # (the integer rows are those of every format)
+            if len(_large_values) >= 3:
+                _large_values.clear()
+            _large_values[rows, seed] = large_content(rows, seed)
+        stored = encode(_large_values[rows, seed], fmt)
+        want = mirror(stored, fmt)
+        stored.setflags(write=False)
+        want.setflags(write=False)
+        _large[key] = (stored, want)
+    return _large[key]
+
+
+def large_cases():
+    """the cases of pz_ego_rows past one grid stride: 7 formats x (4 flat + 5 element-by-element layouts); one content per path"""
+    cases = []
+    for fmt in FORMATS:
+        size = STORAGE[fmt]().itemsize
+        for layouts, rows, seed in ((LARGE_FLAT, LARGE_ROWS[size], 1), (LARGE_PITCHED, LARGE_ROWS["pitched"], 2)):
+            for ip, op, ioff, ooff, inplace in layouts:
+                cases.append(dict(fmt=fmt, rows=rows, in_pitch=ip, out_pitch=op, in_offset=ioff, out_offset=ooff, inplace=inplace, seed=seed,
+                                  large=True))
+    return cases
+
+
+LARGE_CASES = large_cases()
+
+
+def mirror_elements(values, cols, fmt):
+    """the mirror element by element: `values` (any shape, the format's storage type) each done as an element of column
+    `cols` (same shape).  With ``cols = index mod 35`` this is :func:`mirror` (tests/test_ego_host.py holds the two to each
+    other); with the column a mutated walk holds, what that walk stores."""
+    values, cols = np.asarray(values), np.asarray(cols)
+    assert values.dtype == STORAGE[fmt] and values.shape == cols.shape
+    is_court, is_sign = np.isin(np.arange(DIM), COURT), np.isin(np.arange(DIM), SIGN)
+    shape, values, cols = values.shape, np.ascontiguousarray(values).reshape(-1), np.ascontiguousarray(cols).reshape(-1)
+    out = values.copy()
+    at = np.flatnonzero((is_court | is_sign)[cols])          # (8 columns of 35: the others are copied)
+    v, j = values[at], cols[at]
+    if fmt in (0, 2):
+        out[at] = (np.where(is_court[j], WIDTH, 0) - v.astype(np.int64)).astype(values.dtype)
+        return out.reshape(shape)
+    if fmt in NORMALISED:
+        c = np.where(j == 26, C26, np.float32(1.0)).astype(np.float32)
+    else:
+        c = np.where(is_court[j], np.float32(WIDTH), np.float32(0)).astype(np.float32)
+    out[at] = narrow(c - widen(v, fmt), fmt)
+    return out.reshape(shape)
+
+
+def walked_buffer(case, cols, times, buffers=None):
+    """the output buffer after a walk that does element e of the rows (row-major, 35 to a row) `times[e]` times, each time as an
+    element of column `cols[e]`: an element never done keeps what the buffer held (the sentinel; in place the input), one done
+    twice is, in place, the mirror of the mirror -- provided the second visit reads what the first one stored"""
+    src, dst, stored = case_buffers(case) if buffers is None else buffers
+    fmt, rows = case["fmt"], case["rows"]
+    cols, times = np.asarray(cols).reshape(rows, DIM), np.asarray(times).reshape(rows, DIM)
+    out = src.copy() if dst is None else dst.copy()
+    pitch = case["in_pitch"] if dst is None else case["out_pitch"]
+    view = _rows_of(out, GUARD + (case["in_offset"] if dst is None else case["out_offset"]), rows, pitch)
+    once = mirror_elements(stored, cols, fmt)
+    result = np.where(times >= 2, mirror_elements(once, cols, fmt), once) if dst is None else once
+    view[:, :DIM] = np.where(times == 0, view[:, :DIM], bits(result))
     return out
 
 

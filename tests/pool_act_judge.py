@@ -81,6 +81,19 @@ def cases():
     return out
 
 
+def wide_case():
+    """(the case, observations, parameters, members) of tests/test_gpu_wide_pitch.py: 40 rows 2^31 elements apart, float16
+    observations, three members round-robin for both agents (int32 and int64 member vectors), and per agent one row of an
+    invalid member -- agent 1's below the limit, agent 2's behind it.  act_judge.CAP(40) is one row; the draw and the seed are
+    picked so that the float32 restatement has no ambiguous row at all (tests/test_pool_act_host.py asserts it)."""
+    case = dict(K=35, H=64, O=19, A=18, activation="relu", obs_dtype="float16", action_dtype="int64", n=40, P=3, kinds=("round_robin", "round_robin"),
+                turn=1, stats=(True, True), obs_extra=0, head_extra=0, offset=0, draw=2, seed=70)
+    obs, params = case_inputs(case)
+    members = case_members(case)
+    members[0][5], members[1][38] = -1, -1
+    return case, obs, params, members
+
+
 def case_members(case):
     """per agent the typed member vector of a case, or None"""
     return PJ.case_members(case, case["turn"])

@@ -267,6 +267,22 @@ def test_the_restatement_passes_and_stays_inside_the_cap(unmutated):
         assert max(amb) <= AJ.CAP(n)
 
 
+def test_the_wide_pitch_case_has_no_ambiguous_row():
+    """tests/test_gpu_wide_pitch.py runs the act launch on 40 rows; CAP(40) = 1 is a condition on the case, so the case is
+    picked to need none of it: the restatement passes with zero ambiguous rows for both agents"""
+    c = AJ.WIDE_CASE
+    K, H, O, A = c["size"]
+    obs, params = AJ.wide_case_inputs()
+    got = AJ.restate_float32(obs, params, c["activation"], A, AJ.DRAWS[c["draw"]])
+    us = AJ.uniforms(AJ.DRAWS[c["draw"]], c["n"])
+    assert AJ.CAP(c["n"]) == 1
+    for s in (0, 1):
+        amb, fails = AJ.verdict(got[s], obs[s], params[s], c["activation"], A, us[s], what=f"wide case side {s}")
+        print(f"wide case n = {c['n']} side {s}: {amb} ambiguous rows, share {amb / c['n']:.5f}")
+        assert not fails and amb == 0, (s, amb, fails)
+        assert len(set(got[s]["actions"].tolist())) > 4 and len(set(got[s]["actions"][-3:].tolist())) > 1   # (a draw worth judging)
+
+
 @pytest.mark.parametrize("mutant", AJ.MUTANTS)
 def test_every_mutant_is_caught_by_the_gpu_tests_cases(mutant):
     caught = {index: fails for index, (_, fails) in run_cases(mutant).items() if fails}

@@ -2,7 +2,11 @@
 formulation and against torch's CPU bfloat16; the involutions; the header's five bounds on the distance from "normalise the
 mirrored integer", exhaustively over each mirrored column's bounds; the MEANING of the mirror through the oracle's observe on
 planted states; ``PI`` derived from the key table and from SimplifyAction's tuples; every mutant of the judge caught by the GPU
-test's own cases; and the library: exports, build id, lazy loading, the new build tuple, the kernel census, every return code
+test's own cases; a numpy model of the kernels' three index walks, with the grid cap read from the source, which holds that no
+case of the first table takes a thread round its loop, that every large case takes every thread round twice and some a third
+time, and that four mutants of the walks and an actions loop of one trip are caught by the large cases alone (the
+element-by-element ones only in place: out of place an element done twice is stored twice with the same value); and the
+library: exports, build id, lazy loading, the new build tuple, the kernel census, every return code
 that needs no launch in the header's order, and every ValueError of the binding and the wrapper.
 
 No call here ever passes every check with rows to run: a call that passes them all has rows = 0 and launches nothing (so the
@@ -244,6 +248,19 @@ def test_pi_is_the_key_table_with_left_and_right_swapped():
 
 # ---- the cases of the GPU test and the mutants ------------------------------------------------------------------------------------
 CASES = EJ.row_cases()
+LARGE = EJ.LARGE_CASES
+SOURCE = (REPO / "pika-zoo_amd" / "csrc" / "pz_ego.hip").read_text()
+
+
+def source_constant(name):
+    """a ``constexpr int`` of pz_ego.hip, read from its text: a change of the cap must move the model below with it"""
+    found = re.findall(rf"^constexpr int {name} = (\d+);", SOURCE, re.M)
+    assert len(found) == 1, (name, found)
+    return int(found[0])
+
+
+K_THREADS, K_MAX_BLOCKS = source_constant("kThreads"), source_constant("kMaxBlocks")
+STRIDE = K_THREADS * K_MAX_BLOCKS            # threads of a capped grid
 
 
 def test_the_case_table_holds_what_the_kernel_can_get_wrong():
@@ -265,6 +282,32 @@ def test_the_case_table_holds_what_the_kernel_can_get_wrong():
         seen = set(EJ.action_case(dtype, 257).tolist())
         assert seen == set(EJ.action_values(dtype).tolist()) >= set(range(18)) | {18}
     assert (1 << 32) + 3 in EJ.action_values(np.int64) and 255 in EJ.action_values(np.uint8) and -1 in EJ.action_values(np.int16)
+    # the second table: the same formats past one grid stride (what it reaches that the first cannot: the walks below)
+    assert EJ.row_cases() == CASES and not any(c.get("large") for c in CASES) and all(c["large"] for c in LARGE)
+    assert max(c["rows"] for c in CASES) * EJ.DIM < STRIDE
+    for fmt in EJ.FORMATS:
+        mine = [c for c in LARGE if c["fmt"] == fmt]
+        size = EJ.STORAGE[fmt]().itemsize
+        flat, pitched = [c for c in mine if is_flat(c)], [c for c in mine if not is_flat(c)]
+        assert len(flat) == 4 and len(pitched) == 5 and {c["rows"] for c in flat} == {EJ.LARGE_ROWS[size]}
+        assert {c["rows"] for c in pitched} == {EJ.LARGE_ROWS["pitched"]}
+        assert {(c["in_offset"], c["inplace"]) for c in flat} == {(0, False), (0, True), (1, False), (35, True)}
+        assert {flat_split(c)[0] for c in flat} == ({0, 3, 1} if size == 4 else {0, 7, 5})
+        assert all(flat_split(c)[2] - flat_split(c)[0] - flat_split(c)[1] * (16 // size) > 0 for c in flat if c["in_offset"] == 1)   # (a tail)
+        assert {(c["in_pitch"], c["out_pitch"], c["inplace"]) for c in pitched} == {(35, 35, False), (36, 35, False), (35, 40, False), (40, 40, True),
+                                                                                     (36, 36, True)}
+    for c in LARGE:
+        assert not c["inplace"] or (c["in_pitch"], c["in_offset"]) == (c["out_pitch"], c["out_offset"])
+    values = EJ.large_content(4001, 1)
+    kind = (np.arange(4001) + 1) % 4
+    assert (values[kind == 0] == EJ.LOW).all() and (values[kind == 1] == EJ.HIGH).all() and ((values >= EJ.LOW) & (values <= EJ.HIGH)).all()
+    assert not (values[kind >= 2][:, list(EJ.COURT)] == EJ.WIDTH // 2).any()
+    assert all(len(set(row - EJ.LOW)) >= 12 for row in values[kind >= 2][:64])              # (a row's columns differ)
+    assert (EJ.bf16_to_f32(EJ.encode(values, 4)) > 256).sum() >= 5 * 1000
+    assert EJ.LARGE_ACTION_COUNT % 2 == 1 and 2 * STRIDE < EJ.LARGE_ACTION_COUNT < 3 * STRIDE
+    for dtype in EJ.ACTION_DTYPES:
+        behind = EJ.action_case(dtype, EJ.LARGE_ACTION_COUNT)[2 * STRIDE:]
+        assert set(behind.tolist()) == set(EJ.action_values(dtype).tolist())               # (every value on the third trip too)
 
 
 @pytest.mark.parametrize("mutant", EJ.MUTANTS)
@@ -280,6 +323,204 @@ def test_every_mutant_is_caught_by_the_gpu_tests_cases(mutant):
         assert formats == [1, 5, 6]
     else:
         assert formats == list(EJ.FORMATS)
+
+
+# ---- the three index walks of pz_ego.hip past one grid stride ----------------------------------------------------------------------
+# WHY A SECOND TABLE.  Every case of row_cases() and every count of ACTION_COUNTS is done in ONE trip of the kernels' grid-stride
+# loops (held below), so `col = wrap(col + step)`, the (row_step, col_step, carry) walk and the stride itself run in none of
+# them.  The model below restates blocks_for and the three walks over whole thread arrays, with the cap read from the source, and
+# holds LARGE_CASES to what they are there for: two trips for every thread, a third for some, the last trip partial.
+WALK_MUTANTS = ("flat: col not advanced", "flat: step from the stride without V", "pitched: carry dropped", "pitched: col_step dropped")
+
+
+def is_flat(case):
+    """launch_rows' choice: rows back to back and both bases of one phase within 16 bytes (the GPU test's buffers are 256-byte
+    aligned and the guard is a multiple of 16 bytes)"""
+    size = EJ.STORAGE[case["fmt"]]().itemsize
+    assert (EJ.GUARD * size) % 16 == 0
+    return case["in_pitch"] == case["out_pitch"] == EJ.DIM and ((case["in_offset"] - case["out_offset"]) * size) % 16 == 0
+
+
+def blocks_for(threads):
+    return min(max(-(-threads // K_THREADS), 1), K_MAX_BLOCKS)
+
+
+def flat_split(case):
+    """launch_rows: (head, vectors, total)"""
+    size = EJ.STORAGE[case["fmt"]]().itemsize
+    total = case["rows"] * EJ.DIM
+    head = min(((16 - (case["in_offset"] * size) % 16) & 15) // size, total)
+    return head, (total - head) // (16 // size), total
+
+
+def wrap(col):
+    return np.where(col >= EJ.DIM, col - EJ.DIM, col)
+
+
+def flat_walk(case, mutant=None):
+    """rows_flat_kernel: (the column the walk holds for every element, how often the element is done, the trips of every thread)"""
+    V = 16 // EJ.STORAGE[case["fmt"]]().itemsize
+    head, vectors, total = flat_split(case)
+    stride = blocks_for(max(vectors, 2 * V)) * K_THREADS
+    gid = np.arange(stride, dtype=np.int64)
+    body_end = head + vectors * V
+    cols, times, trips = np.full(total, -1, np.int64), np.zeros(total, np.int64), np.zeros(stride, np.int64)
+    edge = gid[gid < head + (total - body_end)]
+    e = np.where(edge < head, edge, body_end + (edge - head))
+    cols[e] = e % EJ.DIM
+    times[e] += 1
+    v = gid[gid < vectors]
+    mine = v.copy()
+    col = (head + v * V) % EJ.DIM
+    step = (stride % EJ.DIM) if mutant == "flat: step from the stride without V" else (stride * V) % EJ.DIM
+    while (v < vectors).any():
+        on = v < vectors
+        for i in range(V):
+            at = head + v[on] * V + i
+            cols[at] = wrap(col[on] + i)
+            times[at] += 1                     # (a trip's elements are distinct)
+        trips[mine[on]] += 1
+        v = v + stride
+        if mutant != "flat: col not advanced":
+            col = wrap(col + step)
+    return cols, times, trips
+
+
+def pitched_walk(case, mutant=None):
+    """rows_pitched_kernel: the same three"""
+    rows, total = case["rows"], case["rows"] * EJ.DIM
+    stride = blocks_for(total) * K_THREADS
+    gid = np.arange(stride, dtype=np.int64)
+    row = gid // EJ.DIM
+    col = gid - row * EJ.DIM
+    row_step = stride // EJ.DIM
+    col_step = stride - row_step * EJ.DIM
+    cols, times, trips = np.full(total, -1, np.int64), np.zeros(total, np.int64), np.zeros(stride, np.int64)
+    while (row < rows).any():
+        on = row < rows
+        at = row[on] * EJ.DIM + col[on]
+        assert len(np.unique(at)) == len(at)
+        cols[at] = col[on]
+        times[at] += 1
+        trips[on] += 1
+        row = row + row_step
+        if mutant != "pitched: col_step dropped":
+            col = col + col_step
+        carry = col >= EJ.DIM
+        col = np.where(carry, col - EJ.DIM, col)
+        if mutant != "pitched: carry dropped":
+            row = row + carry
+    return cols, times, trips
+
+
+_walks, _large_walks = {}, {}
+
+
+def walk_key(case, mutant=None):
+    """what a walk depends on: the kernel, and for the flat one the element size and the head"""
+    flat = is_flat(case)
+    if mutant is not None and mutant.startswith("flat") != flat:
+        mutant = None                          # (a mutant of the other kernel)
+    return (flat, EJ.STORAGE[case["fmt"]]().itemsize if flat else 0, case["rows"], flat_split(case)[0] if flat else 0, mutant)
+
+
+def walk(case, mutant=None):
+    """the walk of a case's launch under `mutant`, made once per key (of the large ones the last six are kept)"""
+    key = walk_key(case, mutant)
+    held = _large_walks if case.get("large") else _walks
+    if key not in held:
+        if case.get("large") and len(held) >= 6:
+            del held[next(iter(held))]
+        cols, times, trips = (flat_walk if key[0] else pitched_walk)(case, key[4])
+        held[key] = (cols.astype(np.int8), times.astype(np.int8), trips)
+    return held[key]
+
+
+def by_size(cases):
+    """the cases in an order that makes every large row set once"""
+    return sorted(cases, key=lambda c: (c["fmt"], c["rows"], c["seed"]))
+
+
+def test_the_constants_of_the_walk_are_the_sources():
+    assert (K_THREADS, K_MAX_BLOCKS, STRIDE) == (256, 2048, 524288), "the cap moved: check that LARGE_CASES still pass two trips (the tests below say)"
+    assert "blocks > kMaxBlocks ? kMaxBlocks : blocks" in SOURCE and "(threads + kThreads - 1) / kThreads" in SOURCE
+    assert "const int step = (int)((stride * V) % kDim);" in SOURCE and "const int64_t row_step = stride / kDim;" in SOURCE
+
+
+def test_the_element_by_element_mirror_is_the_judges():
+    for fmt in EJ.FORMATS:
+        stored = EJ.encode(EJ.large_content(403, 3), fmt)
+        cols = np.tile(np.arange(EJ.DIM), (403, 1))
+        assert np.array_equal(EJ.bits(EJ.mirror_elements(stored, cols, fmt)), EJ.bits(EJ.mirror(stored, fmt))), fmt
+        assert np.array_equal(EJ.bits(EJ.mirror_elements(stored, np.full_like(cols, 1), fmt)), EJ.bits(stored)), fmt
+        moved = EJ.bits(EJ.mirror_elements(stored, (cols + 22) % EJ.DIM, fmt)) != EJ.bits(EJ.mirror(stored, fmt))
+        kind = np.array([(3 if j == 26 and fmt in EJ.NORMALISED else 1) if j in EJ.COURT else 2 if j in EJ.SIGN else 0 for j in range(EJ.DIM)])
+        differs = kind != kind[(np.arange(EJ.DIM) + 22) % EJ.DIM]
+        assert np.array_equal(moved.any(axis=0), differs) and differs.sum() >= 10, fmt   # a mirror in a column of another kind shows
+
+
+def test_every_walk_does_every_element_once_in_its_column_and_only_the_large_cases_stride():
+    seen = set()
+    for case in CASES + by_size(LARGE):
+        if walk_key(case) in seen:
+            continue
+        seen.add(walk_key(case))
+        cols, times, trips = walk(case)
+        assert (times == 1).all() and np.array_equal(cols, np.arange(len(cols)) % EJ.DIM), case
+        if case.get("large"):
+            assert len(trips) == STRIDE and trips.min() >= 2 and trips.max() >= 3, (case, trips.min(), trips.max())
+            assert 0 < (trips == trips.max()).sum() < STRIDE, case                     # the last trip is partial
+        else:
+            # no case of the first table takes a thread round its loop: the reason the second table exists
+            assert trips.max() == 1 and len(trips) < STRIDE, (case, trips.max())
+    print({("flat" if is_flat(c) else "pitched", c["rows"]): np.bincount(walk(c)[2]).tolist() for c in LARGE if c["fmt"] in (0, 2)})
+    for n in EJ.ACTION_COUNTS:
+        assert n <= blocks_for(n) * K_THREADS < STRIDE
+    assert blocks_for(EJ.LARGE_ACTION_COUNT) * K_THREADS == STRIDE and 2 * STRIDE < EJ.LARGE_ACTION_COUNT < 3 * STRIDE
+
+
+@pytest.mark.parametrize("mutant", WALK_MUTANTS)
+def test_every_mutant_of_the_walks_is_caught_by_the_large_cases_and_by_no_other(mutant):
+    """each mutant as the buffer it would leave: the flat ones mirror in wrong columns from the second trip on; the pitched ones
+    do elements twice -- they skip none: trip t of either does rows [t * row_step, (t + 1) * row_step) whole and a part of row
+    (t + 1) * row_step, which trip t + 1 does again"""
+    for case in CASES:
+        for got, want in zip(walk(case, mutant), walk(case)):
+            assert np.array_equal(got, want), (mutant, case)                           # one trip: the walk is the unmutated one
+    for case in [c for c in CASES if c["fmt"] in (1, 6) and c["rows"] in (9, 257)]:
+        cols, times, _ = walk(case, mutant)
+        assert np.array_equal(EJ.walked_buffer(case, cols, times), EJ.expected_buffer(case)), (mutant, case)
+    caught, missed = [], []
+    for case in by_size(LARGE):
+        if mutant.startswith("flat") != is_flat(case):
+            continue
+        cols, times, _ = walk(case, mutant)
+        buffers = EJ.case_buffers(case)
+        same = np.array_equal(EJ.walked_buffer(case, cols, times, buffers), EJ.expected_buffer(case, buffers=buffers))
+        (missed if same else caught).append(case)
+    print(mutant, "caught by", len(caught), "large cases, missed by", len(missed))
+    if mutant.startswith("flat"):
+        assert len(caught) == 4 * len(EJ.FORMATS) and not missed            # every flat case of every format
+        return
+    # Out of place an element done twice is stored twice with the same value: nothing shows.  In place the second visit reads
+    # what the first one stored, and the element is mirrored back (exactly in the integer formats and raw float16; elsewhere
+    # the mirror of the mirror, which differs from the mirror all the same).  So ONLY the in-place cases can catch a pitched
+    # mutant -- and they do so on the device only where the second visit comes after the first one's store: the two visits are
+    # by different workgroups (the grid's first and its last), which this model runs one after the other (on the MI355X both
+    # mutants, built locally, failed the (40, 40) in-place case in every format, in the doubled elements of both rows).
+    assert caught and all(c["inplace"] for c in caught) and all(not c["inplace"] for c in missed)
+    assert {c["fmt"] for c in caught} == set(EJ.FORMATS) and len(caught) == 2 * len(EJ.FORMATS)
+    assert (walk(caught[0], mutant)[1] >= 1).all() and (walk(caught[0], mutant)[1] == 2).sum() >= 2 * 23   # none skipped; 23 per later trip
+
+
+def test_an_actions_loop_of_one_trip_is_caught_by_the_large_count_and_by_no_other():
+    for dtype in EJ.ACTION_DTYPES:
+        for n in EJ.ACTION_COUNTS + (EJ.LARGE_ACTION_COUNT,):
+            a = EJ.action_case(dtype, n)
+            done = np.arange(n) < blocks_for(n) * K_THREADS
+            for before in (a, np.full(n, 99, dtype)):                   # in place; out of place
+                left = np.where(done, EJ.mirror_actions(a), before)
+                assert np.array_equal(left, EJ.mirror_actions(a)) == (n != EJ.LARGE_ACTION_COUNT), (dtype, n)
 
 
 # ---- the library -----------------------------------------------------------------------------------------------------------------

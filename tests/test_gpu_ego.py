@@ -3,7 +3,13 @@ tests/ego_judge.py -- 7 formats x 11 row counts x 18 layouts of pitches, base of
 slab -- equal to the judge bit for bit with every sentinel and every element of pitch padding intact; the overlap code with
 nothing written; ``pz_ego_actions`` in the four action types; the binding into a slot of a rollout buffer and under a captured
 graph; ``wrappers.EgocentricObservation`` on real envs of both state formats against a twin env with the same seed and
-actions; and both examples with and without ``egocentric``."""
+actions; and both examples with and without ``egocentric``.
+
+PAST ONE GRID STRIDE.  The kernels cap their grid at 2 048 workgroups of 256 and stride; every case above is done in one trip
+of their loops (tests/test_ego_host.py proves it on a model of the walks), so the advance of the column, the (row, column) walk
+with its carry and the stride ran in none of them.  ``LARGE_CASES`` (7 formats x 9 layouts at about 2.5 strides, in-place
+element-by-element calls among them: out of place an element done twice is stored twice with the same value and passes),
+the large actions count, a ``[8, 40 001, 35]`` trajectory slab through the binding and one captured replay of each run them."""
 import sys
 from pathlib import Path
 
@@ -115,6 +121,100 @@ def test_actions_go_through_pi_and_other_values_pass(ego, dtype):
     assert ego.mirror_actions(values).cpu().numpy().tolist()[:18] == list(EJ.PI)
     assert torch.equal(ego.mirror_actions(ego.mirror_actions(values)), values)
     assert ego.mirror_actions(values, out=values) is values and values.cpu().numpy().tolist()[18:] == EJ.action_values(dtype).tolist()[18:]
+
+
+# ---- past one grid stride --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", list(EJ.FORMATS))
+def test_large_rows_equal_the_judge_between_the_guards(ego, fmt):
+    """LARGE_CASES as above, one case on the device at a time: every thread of the launch takes two trips and some a third"""
+    lib = ego.load()
+    cases = [c for c in EJ.LARGE_CASES if c["fmt"] == fmt]
+    assert len(cases) == len(EJ.LARGE_FLAT) + len(EJ.LARGE_PITCHED)
+    for case in cases:
+        buffers = EJ.case_buffers(case)
+        src, dst, _ = buffers
+        size = src.dtype.itemsize
+        d_src = upload(src)
+        d_dst = d_src if dst is None else upload(dst)
+        assert d_src.data_ptr() % 256 == 0 and d_dst.data_ptr() % 256 == 0
+        p_in = d_src.data_ptr() + (EJ.GUARD + case["in_offset"]) * size
+        p_out = d_dst.data_ptr() + (EJ.GUARD + case["out_offset"]) * size
+        assert not case["inplace"] or p_in == p_out
+        rc = lib.pz_ego_rows(p_in, p_out, fmt, case["rows"], case["in_pitch"], case["out_pitch"], None)
+        assert rc == 0, (case, rc)
+        torch.cuda.synchronize()
+        want = EJ.expected_buffer(case, buffers=buffers)
+        got = download(d_dst)
+        assert np.array_equal(got, want), (case, np.nonzero(got != want)[0][:8], int((got != want).sum()))
+        if not case["inplace"]:
+            assert np.array_equal(download(d_src), src), case        # the input is read only
+        del d_src, d_dst
+
+
+@pytest.mark.parametrize("dtype", EJ.ACTION_DTYPES)
+def test_large_actions_go_through_pi_on_every_trip(ego, dtype):
+    lib = ego.load()
+    fmt = {np.int32: 0, np.int64: 1, np.uint8: 2, np.int16: 3}[dtype]
+    n = EJ.LARGE_ACTION_COUNT
+    a = EJ.action_case(dtype, n)
+    guard = np.full(16, 77, dtype)
+    want = np.concatenate([guard, EJ.mirror_actions(a), guard])
+    for inplace in (False, True):
+        src = torch.from_numpy(np.concatenate([guard, a, guard])).to(DEV)
+        dst = src if inplace else torch.from_numpy(np.concatenate([guard, np.full(n, 99, dtype), guard])).to(DEV)
+        size = a.dtype.itemsize
+        assert lib.pz_ego_actions(src.data_ptr() + 16 * size, dst.data_ptr() + 16 * size, fmt, n, None) == 0
+        torch.cuda.synchronize()
+        got = dst.cpu().numpy()
+        assert np.array_equal(got, want), (dtype, inplace, np.nonzero(got != want)[0][:8])
+        assert inplace or np.array_equal(src.cpu().numpy()[16:-16], a)
+
+
+def as_rows(host, fmt):
+    t = torch.from_numpy((host.view(np.int16) if host.dtype == np.uint16 else host).copy()).to(DEV)   # (a copy: the shared rows are read-only)
+    return t.view(torch.bfloat16) if fmt in (4, 6) else t
+
+
+def test_mirror_of_a_trajectory_slab_past_one_stride(ego):
+    """"one launch serves a step's [n, 35] and a trajectory's [k, n, 35]" -- here with k * n = 320 008 bfloat16
+    rows, 1.4 million 16-byte pieces, about 2.7 strides of the flat path: in place, and into a slot of a larger buffer"""
+    fmt, k, n = 6, 8, 40001
+    host, want = (x.reshape(k, n, EJ.DIM) for x in EJ.large_rows(fmt, k * n, 3))
+    slab = as_rows(host, fmt)
+    buf = torch.zeros((3, k, n, EJ.DIM), dtype=torch.bfloat16, device=DEV)
+    assert ego.mirror(slab, True, out=buf[1]).data_ptr() == buf[1].data_ptr()
+    torch.cuda.synchronize()
+    assert np.array_equal(stored(buf[1]), want) and not buf[0].any() and not buf[2].any()
+    assert np.array_equal(stored(slab), host)
+    assert ego.mirror(slab, True, out=slab) is slab
+    torch.cuda.synchronize()
+    assert np.array_equal(stored(slab), want)
+
+
+def test_large_launches_under_a_captured_graph(ego):
+    """one replay of the large aligned flat case and of the large actions count; every captured tensor lives until after it"""
+    fmt, n = 1, EJ.LARGE_ROWS[4]
+    host, want = EJ.large_rows(fmt, n, 1)
+    rows = as_rows(np.zeros_like(host), fmt)
+    out = torch.zeros_like(rows)
+    a = EJ.action_case(np.int64, EJ.LARGE_ACTION_COUNT)
+    actions = torch.zeros(len(a), dtype=torch.int64, device=DEV)
+    mapped = torch.zeros_like(actions)
+    ego.mirror(rows, out=out)
+    ego.mirror_actions(actions, out=mapped)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ego.mirror(rows, out=out)
+        ego.mirror_actions(actions, out=mapped)
+    rows.copy_(as_rows(host, fmt))
+    actions.copy_(torch.from_numpy(a).to(DEV))
+    torch.cuda.synchronize()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert np.array_equal(EJ.bits(stored(out)), EJ.bits(want)) and np.array_equal(EJ.bits(stored(rows)), EJ.bits(host))
+    assert np.array_equal(mapped.cpu().numpy(), EJ.mirror_actions(a)) and np.array_equal(actions.cpu().numpy(), a)
+    del graph                                   # (the graph first: rows, out, actions and mapped outlive it)
 
 
 # ---- the binding -----------------------------------------------------------------------------------------------------------------

@@ -3,20 +3,29 @@ lie 2^31 elements and 2^32 bytes apart inside one large allocation (tests/wide_r
 judged by its library's own judge on the rows written.  A kernel that formed ``row * pitch`` in 32 bits would read or write
 somewhere else: the rows behind the limit would be wrong, or a row's guard overwritten.  No GPU result is ever an expected
 value.  Every test frees its large buffer and holds at most 10 GiB of device memory at any time.
+
+The three libraries that came after that work are here too: ``pz_mlp_act`` and ``pz_mlp_act_pool`` (``obs_pitch`` and
+``head_pitch``: their kernels drive the tile through ``tile_layers`` and ``store_tile_float32``, which repeat the forward's text
+beside it, so the forward's test above says nothing about them) and ``pz_ego_rows`` (``in_pitch`` and ``out_pitch`` of the
+element-by-element kernel, in place too).  Their 40-row cases are picked to have no ambiguous row (tests/test_act_host.py and
+tests/test_pool_act_host.py assert it).
 """
 import numpy as np
 import pytest
 import torch
 
+import act_judge as AJ
+import ego_judge as EJ
 import gae_judge as GJ
 import league_judge as LJ
 import net_judge as N
 import netgrad_judge as G
 import policy_judge as J
+import pool_act_judge as PA
 import pool_judge as PJ
 import ppo_judge as P
 from test_gpu_policy import SENT, TAIL, check_against_judge, check_gradient, cpu, device_rows, sentinel, stream
-from wide_rows import LIMIT_BYTES, WideRows
+from wide_rows import LIMIT_BYTES, POISON, WideRows
 
 pytestmark = pytest.mark.gpu
 
@@ -345,3 +354,148 @@ def test_league_tally(wide):
     behind = np.arange(n) >= w.first_beyond
     counted = behind & (x["members_p1"] >= 0) & (x["members_p1"] < Pm) & (x["members_p2"] >= 0) & (x["members_p2"] < Pm)
     assert counted.sum() == n - w.first_beyond and (x["buf1"][counted] != 0).all(), "the case tallies a game whose scores lie behind the limit"
+
+
+# ---- pz_mlp_act, pz_mlp_act_pool -----------------------------------------------------------------------------------------------
+def wide_head_rows(w, sides, written=None):
+    """the float32 head rows of both agents out of a wide tensor (the guard behind every row checked by ``get``); the rows that
+    must not be written still hold the poison"""
+    out = []
+    for s in range(sides):
+        got = w.get(s)
+        if written is not None:
+            assert (got[~written[s]] == POISON).all(), f"the head of side {s}: a row of an invalid member was written"
+        out.append(np.ascontiguousarray(got).view(np.float32))
+    return out
+
+
+def test_mlp_act(wide):
+    """(35, 64, 19, 18), two agents on nets of their own: float16 observations at a wide obs_pitch (both agents' rows side by
+    side in one allocation) with a narrow head, then narrow observations with a float32 head at a wide head_pitch"""
+    from pikazoo_amd import act
+    from test_gpu_act import Inputs, pointers, read_head, read_vectors, step_tensor, vectors
+
+    lib = act.load()
+    c = AJ.WIDE_CASE
+    n, (K, H, O, A), activation, draw = c["n"], c["size"], c["activation"], AJ.DRAWS[c["draw"]]
+    assert n == ROWS
+    obs, params = AJ.wide_case_inputs()
+    inp = Inputs(obs, F16, params)
+    us = AJ.uniforms(draw, n)
+    dev = step_tensor(draw)
+
+    def launch(obs_ptrs, obs_pitch, head_ptrs, head_pitch, what):
+        args = list(inp.net_args(activation))
+        args[0], args[1], args[5] = obs_ptrs[0], obs_ptrs[1], obs_pitch
+        a, logp, ent, val = (vectors(2, n, d) for d in (torch.int64, torch.int32, torch.int32, torch.int32))
+        assert lib.pz_mlp_act(*args, A, draw[0], draw[1], draw[2], dev.data_ptr() if dev is not None else None, J.ACTION_DTYPES.index("int64"),
+                              *pointers(a, 2, itemsize=8), *pointers(logp, 2), *pointers(ent, 2), *pointers(val, 2), *head_ptrs, head_pitch,
+                              stream()) == 0
+        torch.cuda.synchronize()
+        a, logp, ent, val = (read_vectors(ts, n, True, f"{what}: {key}") for ts, key in ((a, "actions"), (logp, "log_probs"), (ent, "entropy"),
+                                                                                      (val, "values")))
+        return [dict(actions=a[s].astype(np.int64), log_probs=logp[s].view(np.float32), entropy=ent[s].view(np.float32),
+                     values=val[s].view(np.float32)) for s in (0, 1)]
+
+    def judged(got, heads, what):
+        for s in (0, 1):
+            amb, fails = AJ.verdict(dict(got[s], head=heads[s]), obs[s], params[s], activation, A, us[s], what=f"{what} side {s}")
+            assert not fails, fails
+
+    patterns = [bits16(x, F16) for x in obs]
+    w = wide(n, K, 2, views=2).put(patterns[0], 0).put(patterns[1], 1)
+    heads = [torch.full((n * O + TAIL,), SENT, dtype=torch.int32, device="cuda:0") for _ in (0, 1)]
+    got = launch([w.ptr(0), w.ptr(1)], w.pitch, [h.data_ptr() for h in heads], O, "wide obs_pitch")
+    judged(got, read_head(heads, n, O, O, 0), f"act obs_pitch {w.pitch}")
+    assert all(np.array_equal(w.get(s), patterns[s]) for s in (0, 1)), "an input changed"
+    w = wide(n, O, 4, views=2)
+    got = launch([inp.xs[0][1], inp.xs[1][1]], K, [w.ptr(0), w.ptr(1)], w.pitch, "wide head_pitch")
+    judged(got, wide_head_rows(w, 2), f"act head_pitch {w.pitch}")
+
+
+def test_mlp_act_pool(wide):
+    """the same two pitches with three members round-robin for both agents and, per agent, one row of an invalid member (agent
+    2's behind the limit): its outputs keep the sentinel and its head row the poison"""
+    from pikazoo_amd import act, policy, pool, pool_act
+    from test_gpu_pool_act import Device, draw_args, pointers, read_heads, read_vectors, vectors
+
+    libs = (pool_act.load(), pool.load(), policy.load(), act.load())
+    case, obs, params, members = PA.wide_case()
+    n, K, O, A = case["n"], case["K"], case["O"], case["A"]
+    assert n == ROWS
+    d = Device(libs, case, obs, params, members)
+    assert [np.flatnonzero(~x).tolist() for x in d.written] == [[5], [38]] and w_first_beyond(n) <= 38
+    dev, dargs = draw_args(PA.DRAWS[case["draw"]])
+    on = (True, True)
+
+    def launch(obs_ptrs, obs_pitch, head_ptrs, head_pitch, what):
+        args = list(d.args())
+        args[0], args[1], args[5] = obs_ptrs[0], obs_ptrs[1], obs_pitch
+        a, logp, ent, val = (vectors(2, n, t) for t in (torch.int64, torch.int32, torch.int32, torch.int32))
+        assert libs[0].pz_mlp_act_pool(*args, A, *dargs, J.ACTION_DTYPES.index("int64"), *pointers(a, on, 8), *pointers(logp, on), *pointers(ent, on),
+                                       *pointers(val, on), *head_ptrs, head_pitch, stream()) == 0
+        torch.cuda.synchronize()
+        a, logp, ent, val = (read_vectors(ts, n, on, d.written, f"{what}: {key}") for ts, key in ((a, "actions"), (logp, "log_probs"),
+                                                                                                   (ent, "entropy"), (val, "values")))
+        return [dict(written=d.written[s], actions=a[s].astype(np.int64), log_probs=logp[s].view(np.float32), entropy=ent[s].view(np.float32),
+                     values=val[s].view(np.float32)) for s in (0, 1)]
+
+    def judged(got, heads, what):
+        amb, fails = PA.verdict(case, [dict(got[s], head=heads[s]) for s in (0, 1)], obs, params, members, what=what)
+        assert not fails, fails
+
+    patterns = [bits16(x, F16) for x in obs]
+    w = wide(n, K, 2, views=2).put(patterns[0], 0).put(patterns[1], 1)
+    heads = [torch.full((n * O + TAIL,), SENT, dtype=torch.int32, device="cuda:0") for _ in (0, 1)]
+    got = launch([w.ptr(0), w.ptr(1)], w.pitch, [h.data_ptr() for h in heads], O, "wide obs_pitch")
+    judged(got, read_heads(heads, n, O, O, 0, on, d.written), f"pool act obs_pitch {w.pitch}")
+    assert all(np.array_equal(w.get(s), patterns[s]) for s in (0, 1)), "an input changed"
+    w = wide(n, O, 4, views=2)
+    got = launch([d.xs[0][1], d.xs[1][1]], K, [w.ptr(0), w.ptr(1)], w.pitch, "wide head_pitch")
+    judged(got, wide_head_rows(w, 2, d.written), f"pool act head_pitch {w.pitch}")
+
+
+def w_first_beyond(rows):
+    """the first row of a WideRows of `rows` rows that starts at or beyond the limit"""
+    return rows - min(3, max(1, rows // 8))
+
+
+# ---- pz_ego_rows, element by element -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", (6, 1), ids=("bfloat16 normalised", "float32 normalised"))
+def test_ego_rows(wide, fmt):
+    """wide in_pitch into rows back to back, rows back to back out at a wide out_pitch, and in place on one wide tensor: equal to
+    the judge bit for bit, the guard behind every wide row intact, the input unchanged where the call is out of place"""
+    from pikazoo_amd import ego
+
+    lib = ego.load()
+    n, size = ROWS, EJ.STORAGE[fmt]().itemsize
+    stored = EJ.encode(EJ.large_content(n, 5), fmt)
+    words, want = EJ.bits(stored), EJ.bits(EJ.mirror(stored, fmt))
+    assert (words != want).any(axis=1)[w_first_beyond(n):].all()                   # (the rows behind the limit change)
+    word = torch.int16 if size == 2 else torch.int32
+
+    def narrow_rows(fill=None):
+        t = torch.full((n * EJ.DIM + TAIL,), SENT, dtype=word, device="cuda:0")
+        if fill is not None:
+            t[:n * EJ.DIM] = torch.from_numpy(fill.view(np.int16 if size == 2 else np.int32).reshape(-1).copy()).to("cuda:0")
+        return t
+
+    def read(t):
+        flat = cpu(t)
+        assert (flat[n * EJ.DIM:] == SENT).all(), "a launch wrote behind its output"
+        return flat[:n * EJ.DIM].view(words.dtype).reshape(n, EJ.DIM)
+
+    def rows(p_in, p_out, in_pitch, out_pitch):
+        assert lib.pz_ego_rows(p_in, p_out, fmt, n, in_pitch, out_pitch, stream()) == 0
+        torch.cuda.synchronize()
+
+    w = wide(n, EJ.DIM, size).put(words)
+    out = narrow_rows()
+    rows(w.ptr(), out.data_ptr(), w.pitch, EJ.DIM)
+    assert np.array_equal(read(out), want) and np.array_equal(w.get().view(words.dtype), words), f"in_pitch {w.pitch}"
+    rows(w.ptr(), w.ptr(), w.pitch, w.pitch)
+    assert np.array_equal(w.get().view(words.dtype), want), f"in place at pitch {w.pitch}"
+    src = narrow_rows(words)
+    w = wide(n, EJ.DIM, size)
+    rows(src.data_ptr(), w.ptr(), EJ.DIM, w.pitch)
+    assert np.array_equal(w.get().view(words.dtype), want) and np.array_equal(read(src), words), f"out_pitch {w.pitch}"

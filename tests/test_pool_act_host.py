@@ -355,6 +355,19 @@ def test_the_restatement_passes_and_stays_inside_the_cap(unmutated):
         assert max(amb) <= PA.CAP(n)
 
 
+def test_the_wide_pitch_case_has_no_ambiguous_row():
+    """tests/test_gpu_wide_pitch.py runs the pool-act launch on 40 rows; CAP(40) = 1 is a condition on the case, so the case
+    is picked to need none of it; each agent has exactly one row of an invalid member, one of them behind the 2^31 limit"""
+    case, obs, params, members = PA.wide_case()
+    got = PA.restate_float32(case, obs, params, members)
+    amb, fails = PA.verdict(case, got, obs, params, members, what="wide case")
+    print(f"wide case n = {case['n']}: ambiguous rows per agent {amb}, share {max(amb) / case['n']:.5f}")
+    assert PA.CAP(case["n"]) == 1 and not fails and amb == [0, 0], (amb, fails)
+    assert [np.flatnonzero(~g["written"]).tolist() for g in got] == [[5], [38]]
+    assert all(set(PJ.effective_members(m, case["P"]).tolist()) == {-1, 0, 1, 2} for m in members)
+    assert [str(m.dtype) for m in members] == ["int32", "int64"]
+
+
 @pytest.mark.parametrize("mutant", PA.MUTANTS)
 def test_every_mutant_is_caught_by_the_gpu_tests_cases(mutant):
     caught = {}
