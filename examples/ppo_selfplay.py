@@ -21,6 +21,12 @@ bits of the two launches and draws from the same stream, so the losses are the s
 ``egocentric=True`` (``--egocentric``) makes the env ``EgocentricObservation(NormalizeObservation(SimplifyAction(env)))``:
 ``player_2``'s rows are what ``player_1`` would see in the mirrored game and the 13 relative actions mean the same on both
 sides, so the shared weights learn one task instead of two.  Whether that trains better is what the flag is there to find out.
+``vtrace=True`` (``--vtrace``) recomputes the targets at the start of every epoch after the first: by then the parameters have
+moved and the rollout is off-policy.  One ``model.act`` over all ``(k + 1) * n`` stored observations gives the current values
+and logits, ``policy.log_probs`` the current log-probs of the stored actions, and ``vtrace.targets`` (one launch, into the
+tensors ``learn.gae`` wrote) the V-trace returns and advantages with the stored log-probs as behaviour.  The first epoch keeps
+``learn.gae`` -- there the two are the same bits -- and ``ppo.loss`` keeps the stored log-probs as ``old_log_probs``.  Not with
+``native_batch``, whose buffer keeps no bootstrap observations.
 """
 import argparse
 import sys
@@ -31,12 +37,15 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "pika-zoo_amd"))
 
 from pikazoo_amd import batch, learn, net, optim, pikazoo_v0, policy, ppo  # noqa: E402
+from pikazoo_amd import vtrace as vtrace_targets  # noqa: E402  (the module alone: its library loads on the first call)
 from pikazoo_amd.wrappers import EgocentricObservation, NormalizeObservation, SimplifyAction  # noqa: E402
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True, native_optimizer=True, native_batch=False, fused_act=False, egocentric=False):
+         native_update=True, native_optimizer=True, native_batch=False, fused_act=False, egocentric=False, vtrace=False):
     """Returns the loss of every minibatch update, as floats."""
+    if vtrace and native_batch:
+        raise ValueError("vtrace=True needs the bootstrap observations, which batch.RolloutBuffer (native_batch=True) does not keep")
     torch.manual_seed(seed)
     env = pikazoo_v0.env(num_envs=num_envs, device=device, seed=seed, validate_actions=False)
     # egocentric: relative actions and player_2's rows mirrored -- both sides are ONE task for a net
@@ -54,13 +63,15 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
     n, k = num_envs, steps
     buf = gathered = rewards = terminations = None   # native_batch: the buffers take their shapes from the first policy step
     if not native_batch:
-        buf_obs = {a: torch.empty((k, n, K), dtype=obs[a].dtype, device=device) for a in agents}
+        buf_obs = {a: torch.empty((k + 1 if vtrace else k, n, K), dtype=obs[a].dtype, device=device) for a in agents}   # vtrace: and the bootstrap's
         buf_act = {a: torch.empty((k, n), dtype=torch.int64, device=device) for a in agents}
         buf_logp = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
         buf_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
         buf_rew = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
         buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
-    head = picked = targets = None
+    head = picked = targets = now = None
+    if vtrace:
+        now_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
     losses, policy_step = [], 0
 
     for it in range(iters):
@@ -102,6 +113,8 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
         else:
             for a in agents:
                 buf_val[a][k].copy_(head[a][:, A])
+                if vtrace:
+                    buf_obs[a][k].copy_(obs[a])
             targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
 
         # ---- update: both agents' samples through the one net ----------------------------------------------------------------
@@ -111,6 +124,15 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
             f_adv, f_ret = flat(targets["advantages"]), flat(targets["returns"])
         size = k * n // minibatches
         for epoch in range(epochs):
+            if vtrace and epoch > 0:
+                # off-policy by now: values and log-probs of the CURRENT parameters over the whole buffer (one net launch, one head
+                # launch), then V-trace into the tensors learn.gae wrote -- f_adv and f_ret are views of them
+                now = model.act({a: buf_obs[a].reshape((k + 1) * n, K) for a in agents}, out=now)
+                logp_now, _ = policy.log_probs({a: now[a][:k * n, :A] for a in agents}, f_act)
+                for a in agents:
+                    now_val[a].view(-1).copy_(now[a][:, A])
+                targets = vtrace_targets.targets(buf_rew, now_val, buf_term, buf_logp, {a: logp_now[a].view(k, n) for a in agents},
+                                                 gamma=0.99, lam=0.95, out=targets)
             if not native_batch:
                 order = torch.randperm(k * n, device=device)
             for m in range(minibatches):
@@ -150,7 +172,8 @@ if __name__ == "__main__":
     p.add_argument("--native-batch", action="store_true", help="batch.RolloutBuffer: one store per policy step, one gather per minibatch")
     p.add_argument("--fused-act", action="store_true", help="ActorCritic.act_sample: the net's forward and the sampling in one launch")
     p.add_argument("--egocentric", action="store_true", help="relative actions and player_2's rows mirrored: one net, either side")
+    p.add_argument("--vtrace", action="store_true", help="V-trace targets under the current parameters from the second epoch on")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
          native_optimizer=not args.torch_optimizer, native_batch=args.native_batch, fused_act=args.fused_act,
-         egocentric=args.egocentric)
+         egocentric=args.egocentric, vtrace=args.vtrace)

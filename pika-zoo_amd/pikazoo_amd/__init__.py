@@ -38,16 +38,19 @@
 
     from pikazoo_amd import ego                        # egocentric rows: player_2 sees the court as player_1 does, one launch
     ego.mirror(obs["player_2"], out=buf_obs[t])        # (wrappers.EgocentricObservation does it behind reset and step)
+
+    from pikazoo_amd import vtrace                     # V-trace targets for off-policy samples (learn.gae's bits on-policy), one launch
+    out = vtrace.targets(rewards, values_now, terminations, stored_log_probs, log_probs_now, gamma=0.99, lam=0.95)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` / `pikazoo_amd.ego` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` / `pikazoo_amd.ego` / `pikazoo_amd.vtrace` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

@@ -1,7 +1,7 @@
 """What stands between a learner binding's own argument checks and its C call, defined once: the device index and the raw
 stream of a launch, the launch itself with its error text, the overlap check of outputs against inputs, the tensor-or-dict
 convention of the two agents, and the workspace check.  ``learn``, ``policy``, ``ppo``, ``net``, ``netgrad``, ``optim``,
-``batch``, ``pool``, ``league``, ``act`` and ``pool_act`` use it (``env`` takes :func:`raw_stream` alone); it imports none of
+``batch``, ``pool``, ``league``, ``act``, ``pool_act`` and ``vtrace`` use it (``env`` takes :func:`raw_stream` alone); it imports none of
 them and loads no library.  A helper that belongs to one family of bindings stays in that family's base module
 (``net._rows``, ``policy._check_logits``): this module knows nothing of any kernel."""
 from __future__ import annotations
