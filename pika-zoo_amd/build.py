@@ -22,8 +22,8 @@ eleventh, bound by pikazoo_amd/league.py; the act library (include/pikazoo_act.h
 pikazoo_amd/act.py, which shares csrc/pz_mlp_tile.hpp with the sixth and csrc/pz_policy_rows.hpp with the fourth; the pool-act library
 (include/pikazoo_pool_act.h: pz_mlp_act_pool) a thirteenth, bound by pikazoo_amd/pool_act.py, which shares both headers with the
 twelfth; the ego library (include/pikazoo_ego.h: pz_ego_rows, pz_ego_actions) a fourteenth, bound by pikazoo_amd/ego.py; the
-V-trace library (include/pikazoo_vtrace.h: pz_vtrace) a fifteenth, bound by pikazoo_amd/vtrace.py.  The fifteen compiles are
-independent and run side by side.
+V-trace library (include/pikazoo_vtrace.h: pz_vtrace) a fifteenth, bound by pikazoo_amd/vtrace.py, which shares its scan over
+the trajectory (csrc/pz_traj_scan.hpp) with the third.  The fifteen compiles are independent and run side by side.
 """
 from __future__ import annotations
 
@@ -81,7 +81,7 @@ BUILD_TARGETS = ALL_TARGETS + ((EGO_LIB, EGO_SOURCES),)
 LIBRARY_TARGETS = BUILD_TARGETS + ((VTRACE_LIB, VTRACE_SOURCES),)
 DEPS = [source for _, sources in LIBRARY_TARGETS for source in sources] + [
     CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
-    CSRC / "pz_policy_rows.hpp", CSRC / "pz_mlp_tile.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
+    CSRC / "pz_policy_rows.hpp", CSRC / "pz_mlp_tile.hpp", CSRC / "pz_traj_scan.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
     INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h",
     INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h", INCLUDE / "pikazoo_league.h", INCLUDE / "pikazoo_act.h",
     INCLUDE / "pikazoo_pool_act.h", INCLUDE / "pikazoo_ego.h", INCLUDE / "pikazoo_vtrace.h"]

@@ -3,7 +3,7 @@ stream of a launch, the launch itself with its error text, the overlap check of 
 convention of the two agents, and the workspace check.  ``learn``, ``policy``, ``ppo``, ``net``, ``netgrad``, ``optim``,
 ``batch``, ``pool``, ``league``, ``act``, ``pool_act`` and ``vtrace`` use it (``env`` takes :func:`raw_stream` alone); it imports none of
 them and loads no library.  A helper that belongs to one family of bindings stays in that family's base module
-(``net._rows``, ``policy._check_logits``): this module knows nothing of any kernel."""
+(``net._rows``, ``policy._check_logits``, ``learn._pitch``): this module knows nothing of any kernel."""
 from __future__ import annotations
 
 import torch

@@ -6,8 +6,9 @@
     out["advantages"]["player_1"], out["returns"]["player_1"]                                # float32 [k, N]
 
 ctypes binding of libpikazoo_learn.so (C ABI and the exact arithmetic: include/pikazoo_learn.h), a library of its own
-beside the product library; nothing in the step path imports this module.  There is no torch fallback: a missing or
-stale library raises.
+beside the product library; nothing in the step path imports this module.  It is the base module of the bindings over the
+trajectory tensors: ``vtrace`` imports its argument checks and format tables from here, which loads no library.  There is
+no torch fallback: a missing or stale library raises.
 """
 from __future__ import annotations
 
@@ -47,6 +48,58 @@ def load():
     return _lib
 
 
+# ---- what every binding over the trajectory tensors checks (``vtrace`` imports these: this is the family's base module) ----
+def _agents(keys, x, name):
+    """the tensors of `x`, which must name the agents that ``rewards`` names (`keys`)"""
+    other, ts = _launch.sides(x, name)
+    if other != keys:
+        raise ValueError(f"rewards and {name} must name the same agents in the same order: {keys} and {other}")
+    return ts
+
+
+def _flags(terminations):
+    """the one tensor of flags that the agents share"""
+    if isinstance(terminations, dict):
+        flags = list(terminations.values())
+        if not flags or any(not isinstance(f, torch.Tensor) for f in flags) or any(
+                f.data_ptr() != flags[0].data_ptr() or f.shape != flags[0].shape or f.stride() != flags[0].stride()
+                for f in flags[1:]):
+            raise ValueError("terminations: the agents share one tensor of flags")
+        terminations = flags[0]
+    if not isinstance(terminations, torch.Tensor):
+        raise ValueError(f"terminations must be a tensor, got {type(terminations).__name__}")
+    return terminations
+
+
+def _rows(r0, fn):
+    """(k, n, device) of the first agent's rewards, for the function named `fn`"""
+    if r0.dim() != 2 or r0.shape[0] < 1:
+        raise ValueError(f"rewards must have shape [k, N] with k >= 1, got {tuple(r0.shape)}")
+    if r0.device.type != "cuda":
+        raise ValueError(f"{fn}() runs on the GPU: rewards are on {r0.device}")
+    return int(r0.shape[0]), int(r0.shape[1]), r0.device
+
+
+def _check_tensors(name, ts, shape, dtypes, dev):
+    """every tensor of `ts` has `shape`, lies on `dev` and is of one of `dtypes` -- given a format table, of the first one's
+    dtype where the table knows it"""
+    if isinstance(dtypes, dict):
+        dtypes = (ts[0].dtype,) if ts[0].dtype in dtypes else tuple(dtypes)
+    for t in ts:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        if t.device != dev:
+            raise ValueError(f"{name} are on {t.device}, rewards on {dev}")
+
+
+def _unit(**factors):
+    for name, x in factors.items():
+        if not (math.isfinite(x) and 0.0 <= x <= 1.0):
+            raise ValueError(f"{name} must lie in [0, 1], got {x}")
+
+
 def _pitch(ts, rows, n, what):
     """the row pitch, in elements, that the tensors of `ts` ([rows, n], last dimension contiguous) share"""
     pitches = set()
@@ -57,8 +110,27 @@ def _pitch(ts, rows, n, what):
         if rows > 1 and t.stride(0) < n:
             raise ValueError(f"{what}: rows overlap (row stride {t.stride(0)} < {n})")
     if len(pitches) != 1:
-        raise ValueError(f"{what}: both agents' tensors must have the same row stride, got {sorted(pitches)}")
+        raise ValueError(f"{what}: the tensors must share one row stride, got {sorted(pitches)}")
     return pitches.pop()
+
+
+def _outputs(out, keys, agents, k, n, dev):
+    """(result, its advantages, its returns, their pitch): `out` -- a previous result of the same agents and shapes -- or, for
+    None, fresh float32 [k, n] tensors in the shape of `keys`"""
+    if out is None:
+        adv = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in range(agents)]
+        ret = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in range(agents)]
+        return {"advantages": _launch.shape(keys, adv), "returns": _launch.shape(keys, ret)}, adv, ret, n
+    if not isinstance(out, dict):
+        raise ValueError(f"out= must be a previous result, got {type(out).__name__}")
+    akeys, adv = _launch.sides(out.get("advantages"), "out['advantages']")
+    rkeys, ret = _launch.sides(out.get("returns"), "out['returns']")
+    if akeys != keys or rkeys != keys:
+        raise ValueError(f"out= holds the agents {akeys} / {rkeys}, the call {keys}")
+    for t in adv + ret:
+        if tuple(t.shape) != (k, n) or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"out= must hold float32 [{k}, {n}] tensors on {dev}")
+    return out, adv, ret, _pitch(adv + ret, k, n, "out=")
 
 
 def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, out: Optional[dict] = None):
@@ -75,63 +147,20 @@ def gae(rewards, values, terminations, gamma: float = 0.99, lam: float = 0.95, o
     allocation when ``out`` is the previous result of the same shapes: it can be captured into a graph.  Shape, dtype,
     device and range errors raise ``ValueError`` before any launch.  The outputs must not alias the inputs."""
     keys, rew = _launch.sides(rewards, "rewards")
-    vkeys, val = _launch.sides(values, "values")
-    if vkeys != keys:
-        raise ValueError(f"rewards and values must name the same agents in the same order: {keys} and {vkeys}")
-    if isinstance(terminations, dict):
-        flags = list(terminations.values())
-        if not flags or any(not isinstance(f, torch.Tensor) for f in flags) or any(
-                f.data_ptr() != flags[0].data_ptr() or f.shape != flags[0].shape or f.stride() != flags[0].stride()
-                for f in flags[1:]):
-            raise ValueError("terminations: the agents share one tensor of flags")
-        term = flags[0]
-    else:
-        term = terminations
-    if not isinstance(term, torch.Tensor):
-        raise ValueError(f"terminations must be a tensor, got {type(term).__name__}")
-    r0 = rew[0]
-    if r0.dim() != 2 or r0.shape[0] < 1:
-        raise ValueError(f"rewards must have shape [k, N] with k >= 1, got {tuple(r0.shape)}")
-    k, n = int(r0.shape[0]), int(r0.shape[1])
-    dev = r0.device
-    if dev.type != "cuda":
-        raise ValueError(f"gae() runs on the GPU: rewards are on {dev}")
-    for name, ts, shape, dtypes in (("rewards", rew, (k, n), (r0.dtype,) if r0.dtype in REWARD_FORMATS else tuple(REWARD_FORMATS)),
-                                    ("values", val, (k + 1, n), (val[0].dtype,) if val[0].dtype in VALUE_FORMATS else tuple(VALUE_FORMATS)),
-                                    ("terminations", [term], (k, n), (torch.bool, torch.uint8))):
-        for t in ts:
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
-            if t.dtype not in dtypes:
-                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-            if t.device != dev:
-                raise ValueError(f"{name} are on {t.device}, rewards on {dev}")
+    val = _agents(keys, values, "values")
+    term = _flags(terminations)
+    k, n, dev = _rows(rew[0], "gae")
+    _check_tensors("rewards", rew, (k, n), REWARD_FORMATS, dev)
+    _check_tensors("values", val, (k + 1, n), VALUE_FORMATS, dev)
+    _check_tensors("terminations", [term], (k, n), (torch.bool, torch.uint8), dev)
     gamma, lam = float(gamma), float(lam)
-    for name, x in (("gamma", gamma), ("lam", lam)):
-        if not (math.isfinite(x) and 0.0 <= x <= 1.0):
-            raise ValueError(f"{name} must lie in [0, 1], got {x}")
+    _unit(gamma=gamma, lam=lam)
     rew_pitch, val_pitch = _pitch(rew, k, n, "rewards"), _pitch(val, k + 1, n, "values")
     term_pitch = _pitch([term], k, n, "terminations")
-
-    adv = ret = None
-    if out is not None:
-        a, r = out.get("advantages"), out.get("returns")
-        akeys, adv = _launch.sides(a, "out['advantages']")
-        rkeys, ret = _launch.sides(r, "out['returns']")
-        if akeys != keys or rkeys != keys:
-            raise ValueError(f"out= holds the agents {akeys} / {rkeys}, the call {keys}")
-        for t in adv + ret:
-            if tuple(t.shape) != (k, n) or t.dtype != torch.float32 or t.device != dev:
-                raise ValueError(f"out= must hold float32 [{k}, {n}] tensors on {dev}")
-        out_pitch = _pitch(adv + ret, k, n, "out=")
-    else:
-        adv = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
-        ret = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
-        out_pitch = n
-        out = {"advantages": _launch.shape(keys, adv), "returns": _launch.shape(keys, ret)}
+    out, adv, ret, out_pitch = _outputs(out, keys, len(rew), k, n, dev)
     if n == 0:
         return out
     ptrs = _launch.ptrs
-    _launch.launch(load().pz_gae, _ERRORS, dev, *ptrs(rew), REWARD_FORMATS[r0.dtype], term.data_ptr(), *ptrs(val), VALUE_FORMATS[val[0].dtype],
+    _launch.launch(load().pz_gae, _ERRORS, dev, *ptrs(rew), REWARD_FORMATS[rew[0].dtype], term.data_ptr(), *ptrs(val), VALUE_FORMATS[val[0].dtype],
                    k, n, rew_pitch, term_pitch, val_pitch, out_pitch, gamma, lam, *ptrs(adv), *ptrs(ret))
     return out

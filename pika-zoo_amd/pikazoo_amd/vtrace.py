@@ -6,8 +6,9 @@
     out["advantages"]["player_1"], out["returns"]["player_1"]                    # float32 [k, N]: ppo.loss takes them as they are
 
 ctypes binding of libpikazoo_vtrace.so (C ABI and the exact arithmetic: include/pikazoo_vtrace.h), a library of its own;
-nothing else imports this module.  Where the two log-prob tensors hold the same bits and the clips are >= 1 the result is
-``learn.gae``'s, bit for bit.  There is no torch fallback: a missing or stale library raises.
+nothing else imports this module, and it takes the argument checks of the trajectory tensors from ``learn``.  Where the two
+log-prob tensors hold the same bits and the clips are >= 1 the result is ``learn.gae``'s, bit for bit.  There is no torch
+fallback: a missing or stale library raises.
 """
 from __future__ import annotations
 
@@ -18,11 +19,10 @@ from typing import Optional
 import torch
 
 from . import _launch, _native
+from .learn import REWARD_FORMATS, VALUE_FORMATS, _agents, _check_tensors, _flags, _outputs, _pitch, _rows, _unit
 
 LIB_PATH = _native.PKG_ROOT / "lib" / "libpikazoo_vtrace.so"
 ABI_VERSION = 1
-REWARD_FORMATS = {torch.int32: 0, torch.float32: 1}
-VALUE_FORMATS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 _P = C.c_void_p
 SIGNATURES = {
@@ -47,20 +47,6 @@ def load():
     return _lib
 
 
-def _pitch(ts, rows, n, what):
-    """the row pitch, in elements, that the tensors of `ts` ([rows, n], last dimension contiguous) share"""
-    pitches = set()
-    for t in ts:
-        if n > 1 and t.stride(1) != 1:
-            raise ValueError(f"{what}: the last dimension must be contiguous (stride {t.stride(1)})")
-        pitches.add(max(int(t.stride(0)), n) if rows > 1 else n)
-        if rows > 1 and t.stride(0) < n:
-            raise ValueError(f"{what}: rows overlap (row stride {t.stride(0)} < {n})")
-    if len(pitches) != 1:
-        raise ValueError(f"{what}: the tensors must share one row stride, got {sorted(pitches)}")
-    return pitches.pop()
-
-
 def targets(rewards, values, terminations, behaviour_log_probs, target_log_probs, gamma: float = 0.99, lam: float = 1.0,
             clip_rho: float = 1.0, clip_c: float = 1.0, clip_pg_rho: float = 1.0, out: Optional[dict] = None):
     """V-trace value targets and policy-gradient advantages of one or both agents in one launch (``pz_vtrace``).
@@ -81,77 +67,32 @@ def targets(rewards, values, terminations, behaviour_log_probs, target_log_probs
     dtype, device, stride, range and agent-set errors raise ``ValueError`` before any launch.  The outputs must not alias
     the inputs."""
     keys, rew = _launch.sides(rewards, "rewards")
-    rest = []
-    for name, x in (("values", values), ("behaviour_log_probs", behaviour_log_probs), ("target_log_probs", target_log_probs)):
-        other, ts = _launch.sides(x, name)
-        if other != keys:
-            raise ValueError(f"rewards and {name} must name the same agents in the same order: {keys} and {other}")
-        rest.append(ts)
-    val, lpb, lpt = rest
-    if isinstance(terminations, dict):
-        flags = list(terminations.values())
-        if not flags or any(not isinstance(f, torch.Tensor) for f in flags) or any(
-                f.data_ptr() != flags[0].data_ptr() or f.shape != flags[0].shape or f.stride() != flags[0].stride()
-                for f in flags[1:]):
-            raise ValueError("terminations: the agents share one tensor of flags")
-        term = flags[0]
-    else:
-        term = terminations
-    if not isinstance(term, torch.Tensor):
-        raise ValueError(f"terminations must be a tensor, got {type(term).__name__}")
-    r0 = rew[0]
-    if r0.dim() != 2 or r0.shape[0] < 1:
-        raise ValueError(f"rewards must have shape [k, N] with k >= 1, got {tuple(r0.shape)}")
-    k, n = int(r0.shape[0]), int(r0.shape[1])
-    dev = r0.device
-    if dev.type != "cuda":
-        raise ValueError(f"targets() runs on the GPU: rewards are on {dev}")
-    for name, ts, shape, dtypes in (("rewards", rew, (k, n), (r0.dtype,) if r0.dtype in REWARD_FORMATS else tuple(REWARD_FORMATS)),
-                                    ("values", val, (k + 1, n), (val[0].dtype,) if val[0].dtype in VALUE_FORMATS else tuple(VALUE_FORMATS)),
-                                    ("behaviour_log_probs", lpb, (k, n), (torch.float32,)),
-                                    ("target_log_probs", lpt, (k, n), (torch.float32,)),
-                                    ("terminations", [term], (k, n), (torch.bool, torch.uint8))):
-        for t in ts:
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
-            if t.dtype not in dtypes:
-                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-            if t.device != dev:
-                raise ValueError(f"{name} are on {t.device}, rewards on {dev}")
+    val, lpb, lpt = (_agents(keys, x, name) for name, x in (("values", values), ("behaviour_log_probs", behaviour_log_probs),
+                                                            ("target_log_probs", target_log_probs)))
+    term = _flags(terminations)
+    k, n, dev = _rows(rew[0], "targets")
+    inputs = (("rewards", rew, (k, n), REWARD_FORMATS), ("values", val, (k + 1, n), VALUE_FORMATS),
+              ("behaviour_log_probs", lpb, (k, n), (torch.float32,)), ("target_log_probs", lpt, (k, n), (torch.float32,)),
+              ("terminations", [term], (k, n), (torch.bool, torch.uint8)))
+    for name, ts, shape, dtypes in inputs:
+        _check_tensors(name, ts, shape, dtypes, dev)
     gamma, lam, clip_rho, clip_c, clip_pg_rho = float(gamma), float(lam), float(clip_rho), float(clip_c), float(clip_pg_rho)
-    for name, x in (("gamma", gamma), ("lam", lam)):
-        if not (math.isfinite(x) and 0.0 <= x <= 1.0):
-            raise ValueError(f"{name} must lie in [0, 1], got {x}")
+    _unit(gamma=gamma, lam=lam)
     for name, x in (("clip_rho", clip_rho), ("clip_c", clip_c), ("clip_pg_rho", clip_pg_rho)):
         if not (math.isfinite(x) and 0.0 <= x <= 3.4028234663852886e38):
             raise ValueError(f"{name} must be a finite float32 >= 0, got {x}")
     rew_pitch, val_pitch = _pitch(rew, k, n, "rewards"), _pitch(val, k + 1, n, "values")
     term_pitch = _pitch([term], k, n, "terminations")
     lp_pitch = _pitch(lpb + lpt, k, n, "behaviour_log_probs and target_log_probs")
-
-    if out is not None:
-        if not isinstance(out, dict):
-            raise ValueError(f"out= must be a previous result, got {type(out).__name__}")
-        akeys, pg = _launch.sides(out.get("advantages"), "out['advantages']")
-        rkeys, vs = _launch.sides(out.get("returns"), "out['returns']")
-        if akeys != keys or rkeys != keys or len(pg) != len(rew) or len(vs) != len(rew):
-            raise ValueError(f"out= holds the agents {akeys} / {rkeys}, the call {keys}")
-        for t in pg + vs:
-            if tuple(t.shape) != (k, n) or t.dtype != torch.float32 or t.device != dev:
-                raise ValueError(f"out= must hold float32 [{k}, {n}] tensors on {dev}")
-        out_pitch = _pitch(pg + vs, k, n, "out=")
+    fresh = out is None
+    out, pg, vs, out_pitch = _outputs(out, keys, len(rew), k, n, dev)
+    if not fresh:
         _launch.no_alias([("out['advantages']", t) for t in pg] + [("out['returns']", t) for t in vs],
-                         [(name, t) for name, ts in (("rewards", rew), ("values", val), ("behaviour_log_probs", lpb),
-                                                     ("target_log_probs", lpt), ("terminations", [term])) for t in ts])
-    else:
-        pg = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
-        vs = [torch.empty((k, n), dtype=torch.float32, device=dev) for _ in rew]
-        out_pitch = n
-        out = {"advantages": _launch.shape(keys, pg), "returns": _launch.shape(keys, vs)}
+                         [(name, t) for name, ts, _, _ in inputs for t in ts])
     if n == 0:
         return out
     ptrs = _launch.ptrs
-    _launch.launch(load().pz_vtrace, _ERRORS, dev, *ptrs(rew), REWARD_FORMATS[r0.dtype], term.data_ptr(), *ptrs(val),
+    _launch.launch(load().pz_vtrace, _ERRORS, dev, *ptrs(rew), REWARD_FORMATS[rew[0].dtype], term.data_ptr(), *ptrs(val),
                    VALUE_FORMATS[val[0].dtype], *ptrs(lpb), *ptrs(lpt), k, n, rew_pitch, term_pitch, val_pitch, lp_pitch, out_pitch,
                    gamma, lam, clip_rho, clip_c, clip_pg_rho, *ptrs(vs), *ptrs(pg))
     return out

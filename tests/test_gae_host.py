@@ -46,6 +46,7 @@ def test_learn_library_exports_exactly_its_header(pz_build, learn_lib):
     assert names == sorted(learn.SIGNATURES) == dynamic_pz_symbols(pz_build.LEARN_LIB)
     assert pz_build.library_id(pz_build.LEARN_LIB) == pz_build.source_id() == learn_lib.pz_learn_build_id().decode()
     assert not pz_build.needs_build()
+    assert pz_build.LEARN_SOURCES[0] in pz_build.DEPS and (pz_build.CSRC / "pz_traj_scan.hpp") in pz_build.DEPS
     assert learn_lib.pz_learn_abi_version() == learn.ABI_VERSION == 1
     assert "#define PZ_LEARN_ABI_VERSION 1" in (REPO / "include" / "pikazoo_learn.h").read_text()
     # the product library did not move: its ABI, and none of the new names in it

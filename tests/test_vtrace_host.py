@@ -196,8 +196,12 @@ def test_every_mutant_is_caught_by_the_gpu_tests_own_cases(mutant):
 
 def test_the_case_table_holds_what_the_kernel_can_get_wrong():
     assert J.K_EDGES == GJ.K_EDGES and J.N_EDGES == GJ.N_EDGES and GJ.CHUNK == 8
-    source = (REPO / "pika-zoo_amd" / "csrc" / "pz_vtrace.hip").read_text()
+    csrc = REPO / "pika-zoo_amd" / "csrc"
+    source = (csrc / "pz_traj_scan.hpp").read_text()
     assert re.findall(r"^constexpr int kChunk = (\d+);", source, re.M) == ["8"], "the chunk moved: K_EDGES are the edges of 8"
+    for unit in ("pz_learn.hip", "pz_vtrace.hip"):        # both kernels scan by that one definition: neither has a chunk of its own
+        text = (csrc / unit).read_text()
+        assert '#include "pz_traj_scan.hpp"' in text and not re.search(r"\bkChunk\s*=", text), unit
     assert {s["k"] for s in J.EXACT["k_edges"]} == set(GJ.K_EDGES) and {s["n"] for s in J.EXACT["n_edges"]} == set(GJ.N_EDGES)
     assert {s["pattern"] for s in J.EXACT["flag_patterns"]} == set(GJ.FLAG_PATTERNS)
     assert {(s["rf"], s["vf"]) for s in J.EXACT["formats"]} == {(r, v) for r in GJ.REWARD_DTYPES for v in GJ.VALUE_DTYPES}
@@ -229,6 +233,7 @@ def test_vtrace_library_exports_exactly_its_header(pz_build, lib):
     assert pz_build.LIBRARY_TARGETS[14] == (pz_build.VTRACE_LIB, pz_build.VTRACE_SOURCES)
     assert pz_build.VTRACE_LIB.name == "libpikazoo_vtrace.so" and pz_build.VTRACE_SOURCES == [pz_build.CSRC / "pz_vtrace.hip"]
     assert pz_build.VTRACE_SOURCES[0] in pz_build.DEPS and (pz_build.INCLUDE / "pikazoo_vtrace.h") in pz_build.DEPS
+    assert (pz_build.CSRC / "pz_traj_scan.hpp") in pz_build.DEPS
     for lib_path, _ in pz_build.LIBRARY_TARGETS:
         assert pz_build.library_id(lib_path) == pz_build.source_id(), lib_path
     assert lib.pz_vtrace_abi_version() == vtrace.ABI_VERSION == 1

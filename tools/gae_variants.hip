@@ -3,8 +3,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Ipika-zoo_amd/csrc tools/gae_variants.hip -o tools/bin/gae_variants
 //   tools/bin/gae_variants [rounds]
 //
-// Compiles the library's own translation unit (csrc/pz_learn.hip is included as text: the same Lane / scan_row the product
-// runs) and beside it
+// Compiles the library's own translation unit (csrc/pz_learn.hip is included as text: the same Lane and row arithmetic the
+// product runs, under the same schedule of csrc/pz_traj_scan.hpp) and beside it
 //   pair      both agents in ONE thread: the flags loaded once, two independent chains per lane, half the waves;
 // float32 rewards and values, both agents.  Per cell (games x rows) the forms are launched interleaved, each sample a
 // batch of launches between two HIP events; medians and spread (max - min) over the rounds.  Before a form is timed its
@@ -31,38 +31,50 @@ using namespace pz_learn;
 
 constexpr int RF = PZ_GAE_REWARD_FLOAT32, VF = PZ_GAE_VALUE_FLOAT32;
 
-struct PairChunk {
-    uint32_t r1[kChunk], r2[kChunk], v1[kChunk], v2[kChunk];
-    uint8_t d[kChunk];
+// both agents' lanes as one lane state of the shared schedule (pz_traj_scan.hpp: scan_rows): the flags loaded once
+struct Pair {
+    struct Chunk {
+        uint32_t r1[kChunk], r2[kChunk], v1[kChunk], v2[kChunk];
+        uint8_t d[kChunk];
+    };
+    Lane<RF, VF> s1, s2;  // (the pitches and the flags are s1's)
+
+    __device__ __forceinline__ void scan_row(int64_t t)
+    {
+        const uint8_t d = s1.term[t * s1.term_pitch];
+        s1.scan(t, s1.rew[t * s1.rew_pitch], s1.val[t * s1.val_pitch], d);
+        s2.scan(t, s2.rew[t * s1.rew_pitch], s2.val[t * s1.val_pitch], d);
+    }
+
+    __device__ __forceinline__ void load_chunk(int64_t t0, Chunk& c) const
+    {
+#pragma unroll
+        for (int i = 0; i < kChunk; ++i) {
+            c.r1[i] = s1.rew[(t0 + i) * s1.rew_pitch];
+            c.r2[i] = s2.rew[(t0 + i) * s1.rew_pitch];
+            c.v1[i] = s1.val[(t0 + i) * s1.val_pitch];
+            c.v2[i] = s2.val[(t0 + i) * s1.val_pitch];
+            c.d[i] = s1.term[(t0 + i) * s1.term_pitch];
+        }
+    }
+
+    __device__ __forceinline__ void scan_chunk(int64_t t0, const Chunk& c)
+    {
+#pragma unroll
+        for (int i = kChunk - 1; i >= 0; --i) {
+            s1.scan(t0 + i, c.r1[i], c.v1[i], c.d[i]);
+            s2.scan(t0 + i, c.r2[i], c.v2[i], c.d[i]);
+        }
+    }
 };
 
-__device__ __forceinline__ void load_pair(const Lane<VF>& s1, const Lane<VF>& s2, int64_t t0, PairChunk& c)
-{
-#pragma unroll
-    for (int i = 0; i < kChunk; ++i) {
-        c.r1[i] = s1.rew[(t0 + i) * s1.rew_pitch];
-        c.r2[i] = s2.rew[(t0 + i) * s1.rew_pitch];
-        c.v1[i] = s1.val[(t0 + i) * s1.val_pitch];
-        c.v2[i] = s2.val[(t0 + i) * s1.val_pitch];
-        c.d[i] = s1.term[(t0 + i) * s1.term_pitch];
-    }
-}
-
-__device__ __forceinline__ void scan_pair(Lane<VF>& s1, Lane<VF>& s2, int64_t t0, const PairChunk& c)
-{
-#pragma unroll
-    for (int i = kChunk - 1; i >= 0; --i) {
-        scan_row<RF, VF>(s1, t0 + i, c.r1[i], c.v1[i], c.d[i]);
-        scan_row<RF, VF>(s2, t0 + i, c.r2[i], c.v2[i], c.d[i]);
-    }
-}
-
-// the shipped kernel's control flow (pz_learn.hip: gae_kernel), two chains per lane
+// the shipped kernel's set-up (pz_learn.hip: gae_kernel), two chains per lane
 __global__ void __launch_bounds__(kLanes) gae_pair_kernel(const GaeArgs a)
 {
     const int64_t g = (int64_t)blockIdx.x * kLanes + threadIdx.x;
     if (g >= a.n) return;
-    Lane<VF> s1, s2;
+    Pair p;
+    Lane<RF, VF>&s1 = p.s1, &s2 = p.s2;
     s1.rew = (const uint32_t*)a.rew_p1 + g, s2.rew = (const uint32_t*)a.rew_p2 + g;
     s1.val = (const uint32_t*)a.val_p1 + g, s2.val = (const uint32_t*)a.val_p2 + g;
     s1.term = s2.term = a.term + g;
@@ -71,32 +83,9 @@ __global__ void __launch_bounds__(kLanes) gae_pair_kernel(const GaeArgs a)
     s1.rew_pitch = s2.rew_pitch = a.rew_pitch, s1.term_pitch = s2.term_pitch = a.term_pitch;
     s1.val_pitch = s2.val_pitch = a.val_pitch, s1.out_pitch = s2.out_pitch = a.out_pitch;
     s1.gamma = s2.gamma = a.gamma, s1.gl = s2.gl = a.gl;
-    int64_t t = a.k;
-    s1.v_next = value_of<VF>(s1.val[t * a.val_pitch]), s2.v_next = value_of<VF>(s2.val[t * a.val_pitch]);
+    s1.v_next = value_of<VF>(s1.val[a.k * a.val_pitch]), s2.v_next = value_of<VF>(s2.val[a.k * a.val_pitch]);
     s1.a_next = s2.a_next = 0.0f;
-    for (int rest = a.k % kChunk; rest > 0; --rest) {
-        --t;
-        const uint8_t d = s1.term[t * a.term_pitch];
-        scan_row<RF, VF>(s1, t, s1.rew[t * a.rew_pitch], s1.val[t * a.val_pitch], d);
-        scan_row<RF, VF>(s2, t, s2.rew[t * a.rew_pitch], s2.val[t * a.val_pitch], d);
-    }
-    if (t == 0) return;
-    PairChunk c0, c1;
-    load_pair(s1, s2, t - kChunk, c0);
-    while (t >= 3 * kChunk) {
-        load_pair(s1, s2, t - 2 * kChunk, c1);
-        scan_pair(s1, s2, t - kChunk, c0);
-        load_pair(s1, s2, t - 3 * kChunk, c0);
-        scan_pair(s1, s2, t - 2 * kChunk, c1);
-        t -= 2 * kChunk;
-    }
-    if (t == 2 * kChunk) {
-        load_pair(s1, s2, 0, c1);
-        scan_pair(s1, s2, kChunk, c0);
-        scan_pair(s1, s2, 0, c1);
-    } else {
-        scan_pair(s1, s2, 0, c0);
-    }
+    scan_rows(p, a.k);
 }
 
 }  // namespace variants
