@@ -261,6 +261,7 @@ def fused_options(wrappers) -> dict:
             assert not opt["normalize_obs"], "one NormalizeObservation"
             opt["normalize_obs"] = True
         elif name == "RecordEpisodeStatistics":
+            assert not opt["episode_stats"], "one RecordEpisodeStatistics"
             later_reward = any(n in ("RewardByBallPosition", "RewardInNormalState") for n, _ in stack[idx + 1:])
             assert not (seen_reward_wrapper and later_reward), "statistics between two reward wrappers"
             opt["episode_stats"] = 2 if seen_reward_wrapper else 1
@@ -284,10 +285,11 @@ def fusable(wrappers) -> bool:
 
 def stack_traits(wrappers) -> dict:
     """What a capture has to know about a stack, fusable or not: the size of the action space, whether observations /
-    rewards come out as floats, whether infos carry episode statistics."""
+    rewards come out as floats, whether infos carry episode statistics (of several RecordEpisodeStatistics every one
+    writes ``infos[agent]["episode"]``, the outermost last: that one's is what a capture records)."""
     names = [n for n, _ in wrapper_stack(wrappers)]
-    if names.count("SimplifyAction") > 1 or names.count("RecordEpisodeStatistics") > 1:
-        raise ValueError("captures take at most one SimplifyAction / RecordEpisodeStatistics")
+    if names.count("SimplifyAction") > 1:
+        raise ValueError("captures take at most one SimplifyAction")
     return dict(n_actions=13 if "SimplifyAction" in names else 18,
                 float_obs="NormalizeObservation" in names,
                 float_reward=any(n in ("RewardByBallPosition", "RewardInNormalState") for n in names),
@@ -882,8 +884,69 @@ def capture_png_layout() -> dict:
                 meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
 
 
+def _stack_table():
+    """tests/wrapper_stacks.py: the table of stacks and the run recipe the sweep's tests share with this capture."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("wrapper_stacks", _REPO / "tests" / "wrapper_stacks.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def capture_stack_sweep() -> dict:
+    """The unmodified reference on every stack of tests/wrapper_stacks.py (340: depth one to four over the four
+    reward / observation / statistics wrappers, SimplifyAction at a rotating place), on the first
+    ``FIXTURE_LANES`` games of its run recipe.  {file stem: arrays}:
+
+    * ``stack_sweep_depth<d>``: per stack of that depth (``index``: its number in the table) the rewards
+      ``rew`` [S, T, 2, L] float64, ``term`` [S, T, L] and, where the stack has statistics, ``ep_r`` [S, T, 2, L] /
+      ``ep_l`` [S, T, L] of the outermost RecordEpisodeStatistics on terminal frames (NaN / -1 elsewhere);
+    * ``stack_sweep_shared``: what does not depend on the stack -- per action space (``a18`` / ``a13``: without / with
+      SimplifyAction) the actions and the state words, and per observation pipeline (the number of
+      NormalizeObservations, 0-4, is all the rows depend on: asserted here) the rows ``obs_<a>_<count>`` / after reset
+      ``obs0_<a>_<count>``."""
+    ws = _stack_table()
+    rec, lanes = ws.RECIPE, ws.FIXTURE_LANES
+    T = rec["T"]
+    shared, by_depth = {}, {}
+    for k in range(ws.n_stacks()):
+        st = ws.stack(k)
+        data = capture(f"stack_{k}", lanes, T, seed=rec["seed"], action_seed=rec["action_seed"],
+                       env_id_base=rec["env_id_base"], env_kwargs=dict(winning_score=rec["winning_score"]),
+                       wrappers=dict(stack=[[n, kw] for n, kw in st]), full=True)
+        a = "a13" if ws.simplified(st) else "a18"
+        states = data["states"].astype(np.int32)
+        states[:, po.E_RNG_COUNTER] = data["rng_counter"]
+        count = ws.n_normalize(st)
+        for key, value in ((f"actions_{a}", data["actions"]), (f"states_{a}", states),
+                           (f"state_ctor_{a}", data["state_ctor"]), (f"state0_{a}", data["state0"]),
+                           (f"obs0_{a}_{count}", data["obs_reset"]), (f"obs_{a}_{count}", data["obs"])):
+            if key in shared:  # the part of a run that no reward / statistics wrapper can touch
+                assert shared[key].dtype == value.dtype and np.array_equal(shared[key], value), (k, key)
+            else:
+                shared[key] = value
+        d = by_depth.setdefault(len(ws.all_names()[k]), dict(index=[], rew=[], term=[], ep_r=[], ep_l=[]))
+        d["index"].append(k)
+        d["rew"].append(data["rew"].astype(np.float64))
+        d["term"].append(data["term"])
+        d["ep_r"].append(data.get("ep_r", np.full((T, 2, lanes), np.nan)))
+        d["ep_l"].append(data.get("ep_l", np.full((T, lanes), -1, np.int32)))
+    meta = dict(recipe=rec, lanes=lanes, stacks=ws.n_stacks())
+    out = {"stack_sweep_shared": dict(shared, meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))}
+    for depth, d in by_depth.items():
+        out[f"stack_sweep_depth{depth}"] = dict(index=np.asarray(d["index"], np.int32), rew=np.stack(d["rew"]),
+                                                term=np.stack(d["term"]), ep_r=np.stack(d["ep_r"]),
+                                                ep_l=np.stack(d["ep_l"]).astype(np.int32))
+    return out
+
+
 def write_live_fixtures(only=None):
-    """tests/golden/live_*.npz and reference_png_layout.npz (tests/test_oracle_vs_reference.py, tests/test_render_cpu.py)."""
+    """tests/golden/live_*.npz, stack_sweep_*.npz and reference_png_layout.npz (tests/test_oracle_vs_reference.py,
+    tests/test_wrapper_stacks_host.py, tests/test_render_cpu.py)."""
+    if only in (None, "stack_sweep"):
+        for stem, arrays in capture_stack_sweep().items():
+            np.savez_compressed(GOLDEN / f"{stem}.npz", **arrays)
     for name, kw, wr in LIVE_RUNS:
         if only in (None, f"live_{name}"):
             np.savez_compressed(GOLDEN / f"live_{name}.npz", **capture_live(name, kw, wr))

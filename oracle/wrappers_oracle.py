@@ -30,11 +30,15 @@ class WrappedOracle:
     ``reset()`` -> (obs_p1, obs_p2); ``step(a1, a2)`` -> (obs [2][n, 35], rew [2][n] float64, term [n] uint8,
     episode) with ``episode`` = None or {"r": float64 [2, n], "l": int64 [n]} of the OUTERMOST RecordEpisodeStatistics
     (meaningful where ``term``), as the harness around the reference does it: a finished game is ``reset()`` right before
-    its next step."""
+    its next step.
 
-    def __init__(self, num_envs: int, stack, **env_kwargs):
+    ``env``: instead of an ``OracleEnv`` of its own, any object with that class's ``reset()`` / ``step(a1, a2)`` /
+    ``state`` -- tests/wrapper_stacks.py replays ONE recorded un-wrapped run under every stack of its table."""
+
+    def __init__(self, num_envs: int, stack, env=None, **env_kwargs):
         self.stack = [(name, dict(kw)) for name, kw in stack]
-        self.env = po.OracleEnv(num_envs, po.make_config(auto_reset=True, **env_kwargs))
+        assert env is None or not env_kwargs, "a ready env carries its own configuration"
+        self.env = env if env is not None else po.OracleEnv(num_envs, po.make_config(auto_reset=True, **env_kwargs))
         self.n = num_envs
         # per-wrapper state, in stack order
         self.state = []

@@ -14,6 +14,7 @@ without a GPU raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from typing import Dict, Optional
 
@@ -528,8 +529,9 @@ class raw_env(ParallelEnv):
     # Every _fuse_* method answers whether the kernel took the wrapper over.  False: this stack order cannot be expressed
     # as a kernel branch (the reference composes its wrappers in any order) and the wrapper class applies itself to the
     # step's outputs with torch operations instead -- which puts it OUTSIDE everything fused, exactly where a wrapper
-    # constructed later sits in the reference's stack.  Once one reward wrapper works that way, every later wrapper that
-    # reads rewards must too (`_unfused_reward`).
+    # constructed later sits in the reference's stack.  Once a wrapper that writes OR reads rewards works that way (a
+    # reward wrapper; a RecordEpisodeStatistics, whose sums must not see what a reward wrapper above it does), every later
+    # wrapper that writes or reads rewards must too (`_unfused_reward`): fused, it would move below it.
     def _note_unfused(self, name: str, reward: bool = False):
         if self.frame_skip > 1 and name != "SimplifyAction":
             # (a second SimplifyAction only maps the ACTIONS on their way in, once per step() like the held actions
@@ -555,12 +557,22 @@ class raw_env(ParallelEnv):
         assert len(additional_reward) == 8  # reward_by_ball_position.py:15
         # not as a kernel branch: a second RewardByBallPosition; above NormalizeObservation (it then reads the NORMALIZED
         # ball coordinates, reward_by_ball_position.py:22 -- what the reference does, and what the wrapper class then
-        # does); above statistics that already sum a wrapped reward; above a reward wrapper that runs outside the kernel
+        # does); above statistics that already sum a wrapped reward; above a reward or statistics wrapper that runs outside
+        # the kernel
         if self._cfg.ballpos_reward or self._cfg.normalize_obs in (1, 5, 6) or self._cfg.episode_stats_mode == 2 or \
                 self._unfused_reward or "NormalizeObservation" in self._unfused:
             return False
+        # the kernel compares integer coordinates with integer lines: `x >= x_line` is `x >= ceil(x_line)` and
+        # `y > y_line` is `y > floor(y_line)` for every integer x, y (truncation would turn x >= 216.5 into x >= 216).  A line
+        # that is not a finite number of the int32 range stays with the wrapper class, which compares as the reference does
+        try:
+            x_int, y_int = math.ceil(x_line), math.floor(y_line)
+        except (TypeError, ValueError, OverflowError):
+            return False
+        if not (-2**31 <= x_int < 2**31 and -2**31 <= y_int < 2**31):
+            return False
         self._cfg.ballpos_reward = 1
-        self._cfg.x_line, self._cfg.y_line = int(x_line), int(y_line)
+        self._cfg.x_line, self._cfg.y_line = x_int, y_int
         for i, v in enumerate(additional_reward):
             self._cfg.additional_reward[i] = float(v)
         self._cfg_version += 1
@@ -570,7 +582,7 @@ class raw_env(ParallelEnv):
         """wrappers/reward_in_normal_state.py:10-15 inside the kernel; remembers whether it was applied
         before or after RewardByBallPosition (the reference's result depends on the wrapper order)."""
         if self._cfg.normal_state_mode or self._cfg.episode_stats_mode == 2 or self._unfused_reward:
-            return False  # a second one / above statistics of a wrapped reward / above an unfused reward wrapper
+            return False  # a second one / above statistics of a wrapped reward / above an unfused reward or statistics wrapper
         self._cfg.normal_state_mode = 2 if self._cfg.ballpos_reward else 1
         self._cfg.normal_state_reward = float(reward)
         self._cfg_version += 1
@@ -600,7 +612,7 @@ class raw_env(ParallelEnv):
     def _fuse_episode_stats(self) -> bool:
         """wrappers/record_episode_statistics.py:27-40 inside the kernel (three words per game)."""
         if self._cfg.episode_stats_mode or self._unfused_reward:
-            return False  # a second one / above a reward wrapper that runs outside the kernel
+            return False  # a second one / above a reward or statistics wrapper that runs outside the kernel
         wrapped = bool(self._cfg.ballpos_reward or self._cfg.normal_state_mode)
         self._cfg.episode_stats_mode = 2 if wrapped else 1
         # include/pikazoo_hip.h: double[2][stride] running returns, then int32[stride] episode lengths

@@ -28,7 +28,9 @@ class RecordEpisodeStatistics(BaseParallelWrapper):
         raw = env.unwrapped
         self.fused = raw._fuse_episode_stats()
         if not self.fused:
-            raw._note_unfused("RecordEpisodeStatistics")
+            # reward=True: a reward wrapper constructed above these sums must stay above them -- fused into the kernel it
+            # would shape the rewards they add up
+            raw._note_unfused("RecordEpisodeStatistics", reward=True)
             n = raw.num_envs
             self._returns = torch.zeros((2, n), dtype=torch.float64, device=raw.device)
             self._lengths = torch.zeros(n, dtype=torch.int32, device=raw.device)

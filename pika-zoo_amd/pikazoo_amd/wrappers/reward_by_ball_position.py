@@ -7,10 +7,13 @@ added, ``zone = int(ball_y > y_line) + 2*int(ball_x >= x_line)`` from the post-s
 Normally **fused**: the add runs in the step kernel's epilogue in float32, so the rewards of a wrapped env are
 ``float32[num_envs]``.  Where the stack order cannot be a kernel branch -- a second RewardByBallPosition, one above
 ``NormalizeObservation`` (which, as in the reference, then compares the NORMALIZED coordinates ``obs[26], obs[27]`` with
-the lines, :22-24), one above statistics of a wrapped reward or above another wrapper that runs outside the kernel -- the
-same three lines run here on the step's outputs (``fused`` is False), float32 like the fused form -- but not on
+the lines, :22-24), one above statistics of a wrapped reward or above another reward or statistics wrapper that runs
+outside the kernel -- the same three lines run here on the step's outputs (``fused`` is False), float32 like the fused form -- but not on
 float16 / bfloat16 observation rows, where the constructor raises ValueError instead (the comparison would read
 rounded coordinates).
+
+The lines need not be integers: the kernel compares integer coordinates, so it is handed ``ceil(x_line)`` and
+``floor(y_line)``, which decide ``x >= x_line`` and ``y > y_line`` exactly as the reference's comparison does.
 """
 from __future__ import annotations
 
