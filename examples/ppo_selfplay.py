@@ -27,6 +27,10 @@ and logits, ``policy.log_probs`` the current log-probs of the stored actions, an
 tensors ``learn.gae`` wrote) the V-trace returns and advantages with the stored log-probs as behaviour.  The first epoch keeps
 ``learn.gae`` -- there the two are the same bits -- and ``ppo.loss`` keeps the stored log-probs as ``old_log_probs``.  Not with
 ``native_batch``, whose buffer keeps no bootstrap observations.
+``fused_rollout=True`` (``--fused-rollout``) makes the whole rollout loop ONE launch per iteration: ``ActorCritic.rollout``
+(``env.rollout_policy``) runs the ``k`` policy steps -- net, draw and frame -- and the bootstrap value inside one kernel and
+returns the rollout buffer itself, which ``learn.gae`` reads as it is.  It returns the bits of the loop it replaces and draws
+from the same stream, so the losses are the same numbers.  Off by default; not with ``native_batch`` or ``egocentric``.
 """
 import argparse
 import sys
@@ -42,8 +46,12 @@ from pikazoo_amd.wrappers import EgocentricObservation, NormalizeObservation, Si
 
 
 def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, seed=0, device="cuda:0", log=print,
-         native_update=True, native_optimizer=True, native_batch=False, fused_act=False, egocentric=False, vtrace=False):
+         native_update=True, native_optimizer=True, native_batch=False, fused_act=False, egocentric=False, vtrace=False,
+         fused_rollout=False):
     """Returns the loss of every minibatch update, as floats."""
+    if fused_rollout and (native_batch or egocentric):
+        raise ValueError("fused_rollout=True returns the rollout buffer itself (no batch.RolloutBuffer: native_batch=False) and takes "
+                         "wrappers the step kernel fuses (EgocentricObservation mirrors outside it: egocentric=False)")
     if vtrace and native_batch:
         raise ValueError("vtrace=True needs the bootstrap observations, which batch.RolloutBuffer (native_batch=True) does not keep")
     torch.manual_seed(seed)
@@ -62,60 +70,68 @@ def main(num_envs=1024, iters=4, steps=16, epochs=2, minibatches=4, lr=3e-4, see
 
     n, k = num_envs, steps
     buf = gathered = rewards = terminations = None   # native_batch: the buffers take their shapes from the first policy step
-    if not native_batch:
+    if not native_batch and not fused_rollout:
         buf_obs = {a: torch.empty((k + 1 if vtrace else k, n, K), dtype=obs[a].dtype, device=device) for a in agents}   # vtrace: and the bootstrap's
         buf_act = {a: torch.empty((k, n), dtype=torch.int64, device=device) for a in agents}
         buf_logp = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
         buf_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
         buf_rew = {a: torch.empty((k, n), dtype=torch.float32, device=device) for a in agents}
         buf_term = torch.empty((k, n), dtype=torch.bool, device=device)
-    head = picked = targets = now = None
+    head = picked = targets = now = roll = None
     if vtrace:
         now_val = {a: torch.empty((k + 1, n), dtype=torch.float32, device=device) for a in agents}
     losses, policy_step = [], 0
 
     for it in range(iters):
         # ---- rollout: k policy steps, three launches each (net, head, step), two with fused_act ------------------------------
-        for t in range(k):
-            if fused_act:                                         # one launch: the head only where the buffer stores it
-                picked = model.act_sample(obs, seed=seed, step=policy_step, head=native_batch, out=picked)
-                values = picked["values"]
-                if native_batch:
-                    head = picked["head"]
-            else:
-                head = model.act(obs, out=head)                   # {agent: [n, A + 1]}: logits and value
-                picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
-                values = {a: head[a][:, A] for a in agents}
-            if native_batch:
-                if buf is None:
-                    buf = batch.RolloutBuffer(k, n, dict(obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head),
-                                              minibatches=minibatches, seed=seed)
-                # one launch: this step's records to row t, the outcome of the previous step (what came with obs) to row t - 1
-                buf.store(t, obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head,
-                          rewards=rewards if t else None, terminations=terminations if t else None)
-            else:
-                for a in agents:
-                    buf_obs[a][t].copy_(obs[a])
-                    buf_act[a][t].copy_(picked["actions"][a])
-                    buf_logp[a][t].copy_(picked["log_probs"][a])
-                    buf_val[a][t].copy_(values[a])
-            obs, rewards, terminations, _, _ = env.step(picked["actions"])
-            if not native_batch:
-                for a in agents:
-                    buf_rew[a][t].copy_(rewards[a])
-                buf_term[t].copy_(terminations[agents[0]])
-            policy_step += 1
-        head = model.act(obs, out=head)                           # the bootstrap value
-        if native_batch:
-            buf.store(k, head=head, rewards=rewards, terminations=terminations)
-            targets = learn.gae(buf.rewards, buf.values, buf.terminations, gamma=0.99, lam=0.95, out=targets)
-            buf.set_targets(targets)
-        else:
-            for a in agents:
-                buf_val[a][k].copy_(head[a][:, A])
-                if vtrace:
-                    buf_obs[a][k].copy_(obs[a])
+        if fused_rollout:
+            # ONE launch: k x (net, draw, frame) and the bootstrap value; what it returns IS the rollout buffer
+            roll = model.rollout(env, k, seed=seed, step=policy_step, out=roll)
+            policy_step += k
+            buf_obs, buf_act, buf_logp, buf_val = roll["obs"], roll["actions"], roll["log_probs"], roll["values"]
+            buf_rew, buf_term = roll["rewards"], roll["terminations"]
             targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
+        else:
+            for t in range(k):
+                if fused_act:                                         # one launch: the head only where the buffer stores it
+                    picked = model.act_sample(obs, seed=seed, step=policy_step, head=native_batch, out=picked)
+                    values = picked["values"]
+                    if native_batch:
+                        head = picked["head"]
+                else:
+                    head = model.act(obs, out=head)                   # {agent: [n, A + 1]}: logits and value
+                    picked = policy.sample({a: head[a][:, :A] for a in agents}, seed=seed, step=policy_step, out=picked)
+                    values = {a: head[a][:, A] for a in agents}
+                if native_batch:
+                    if buf is None:
+                        buf = batch.RolloutBuffer(k, n, dict(obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head),
+                                                  minibatches=minibatches, seed=seed)
+                    # one launch: this step's records to row t, the outcome of the previous step (what came with obs) to row t - 1
+                    buf.store(t, obs=obs, actions=picked["actions"], log_probs=picked["log_probs"], head=head,
+                              rewards=rewards if t else None, terminations=terminations if t else None)
+                else:
+                    for a in agents:
+                        buf_obs[a][t].copy_(obs[a])
+                        buf_act[a][t].copy_(picked["actions"][a])
+                        buf_logp[a][t].copy_(picked["log_probs"][a])
+                        buf_val[a][t].copy_(values[a])
+                obs, rewards, terminations, _, _ = env.step(picked["actions"])
+                if not native_batch:
+                    for a in agents:
+                        buf_rew[a][t].copy_(rewards[a])
+                    buf_term[t].copy_(terminations[agents[0]])
+                policy_step += 1
+            head = model.act(obs, out=head)                           # the bootstrap value
+            if native_batch:
+                buf.store(k, head=head, rewards=rewards, terminations=terminations)
+                targets = learn.gae(buf.rewards, buf.values, buf.terminations, gamma=0.99, lam=0.95, out=targets)
+                buf.set_targets(targets)
+            else:
+                for a in agents:
+                    buf_val[a][k].copy_(head[a][:, A])
+                    if vtrace:
+                        buf_obs[a][k].copy_(obs[a])
+                targets = learn.gae(buf_rew, buf_val, buf_term, gamma=0.99, lam=0.95, out=targets)
 
         # ---- update: both agents' samples through the one net ----------------------------------------------------------------
         flat = lambda d: {a: d[a][:k].reshape(k * n, *d[a].shape[2:]) for a in agents}  # noqa: E731
@@ -173,7 +189,8 @@ if __name__ == "__main__":
     p.add_argument("--fused-act", action="store_true", help="ActorCritic.act_sample: the net's forward and the sampling in one launch")
     p.add_argument("--egocentric", action="store_true", help="relative actions and player_2's rows mirrored: one net, either side")
     p.add_argument("--vtrace", action="store_true", help="V-trace targets under the current parameters from the second epoch on")
+    p.add_argument("--fused-rollout", action="store_true", help="ActorCritic.rollout: the k policy steps of an iteration in one launch")
     args = p.parse_args()
     main(num_envs=args.num_envs, iters=args.iters, steps=args.steps, native_update=not args.torch_update,
          native_optimizer=not args.torch_optimizer, native_batch=args.native_batch, fused_act=args.fused_act,
-         egocentric=args.egocentric, vtrace=args.vtrace)
+         egocentric=args.egocentric, vtrace=args.vtrace, fused_rollout=args.fused_rollout)

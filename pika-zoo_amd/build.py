@@ -1,6 +1,6 @@
 """Build libpikazoo_hip.so -- and beside it libpikazoo_diag.so, libpikazoo_learn.so, libpikazoo_policy.so,
 libpikazoo_ppo.so, libpikazoo_net.so, libpikazoo_netgrad.so, libpikazoo_optim.so, libpikazoo_batch.so, libpikazoo_pool.so,
-libpikazoo_league.so, libpikazoo_act.so, libpikazoo_pool_act.so, libpikazoo_ego.so and libpikazoo_vtrace.so -- for gfx950 with hipcc (in-tree, no JIT cache).
+libpikazoo_league.so, libpikazoo_act.so, libpikazoo_pool_act.so, libpikazoo_ego.so, libpikazoo_vtrace.so and libpikazoo_rollout.so -- for gfx950 with hipcc (in-tree, no JIT cache).
 
     python pika-zoo_amd/build.py [--force]
 
@@ -23,7 +23,10 @@ pikazoo_amd/act.py, which shares csrc/pz_mlp_tile.hpp with the sixth and csrc/pz
 (include/pikazoo_pool_act.h: pz_mlp_act_pool) a thirteenth, bound by pikazoo_amd/pool_act.py, which shares both headers with the
 twelfth; the ego library (include/pikazoo_ego.h: pz_ego_rows, pz_ego_actions) a fourteenth, bound by pikazoo_amd/ego.py; the
 V-trace library (include/pikazoo_vtrace.h: pz_vtrace) a fifteenth, bound by pikazoo_amd/vtrace.py, which shares its scan over
-the trajectory (csrc/pz_traj_scan.hpp) with the third.  The fifteen compiles are independent and run side by side.
+the trajectory (csrc/pz_traj_scan.hpp) with the third; the rollout library (include/pikazoo_rollout.h: pz_rollout_policy) a
+sixteenth, bound by pikazoo_amd/rollout.py, which shares the frame and its I/O (csrc/pz_physics.hpp, csrc/pz_step_io.hpp) with the
+first, csrc/pz_mlp_tile.hpp with the sixth and csrc/pz_policy_rows.hpp with the fourth.  The sixteen compiles are independent and
+run side by side.
 """
 from __future__ import annotations
 
@@ -54,6 +57,7 @@ ACT_LIB = LIB_DIR / "libpikazoo_act.so"
 POOL_ACT_LIB = LIB_DIR / "libpikazoo_pool_act.so"
 EGO_LIB = LIB_DIR / "libpikazoo_ego.so"
 VTRACE_LIB = LIB_DIR / "libpikazoo_vtrace.so"
+ROLLOUT_LIB = LIB_DIR / "libpikazoo_rollout.so"
 SOURCES = [CSRC / "pz_kernels.hip"]
 DIAG_SOURCES = [CSRC / "pz_diag.hip"]
 LEARN_SOURCES = [CSRC / "pz_learn.hip"]
@@ -69,6 +73,7 @@ ACT_SOURCES = [CSRC / "pz_act.hip"]
 POOL_ACT_SOURCES = [CSRC / "pz_pool_act.hip"]
 EGO_SOURCES = [CSRC / "pz_ego.hip"]
 VTRACE_SOURCES = [CSRC / "pz_vtrace.hip"]
+ROLLOUT_SOURCES = [CSRC / "pz_rollout.hip"]
 # every library with the translation units it is compiled from
 TARGETS = ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES), (POLICY_LIB, POLICY_SOURCES), (PPO_LIB, PPO_SOURCES),
            (NET_LIB, NET_SOURCES), (NETGRAD_LIB, NETGRAD_SOURCES), (OPTIM_LIB, OPTIM_SOURCES), (BATCH_LIB, BATCH_SOURCES),
@@ -77,14 +82,16 @@ TARGETS = ((LIB, SOURCES), (DIAG_LIB, DIAG_SOURCES), (LEARN_LIB, LEARN_SOURCES),
 ALL_TARGETS = TARGETS + ((ACT_LIB, ACT_SOURCES), (POOL_ACT_LIB, POOL_ACT_SOURCES))
 # ... and the ego library (BUILD_TARGETS keeps its fourteen)
 BUILD_TARGETS = ALL_TARGETS + ((EGO_LIB, EGO_SOURCES),)
-# what build(), needs_build() and DEPS walk: every library there is
+# ... and the V-trace library (LIBRARY_TARGETS keeps its fifteen)
 LIBRARY_TARGETS = BUILD_TARGETS + ((VTRACE_LIB, VTRACE_SOURCES),)
-DEPS = [source for _, sources in LIBRARY_TARGETS for source in sources] + [
-    CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
+# what build(), needs_build() and DEPS walk: every library there is
+EVERY_TARGET = LIBRARY_TARGETS + ((ROLLOUT_LIB, ROLLOUT_SOURCES),)
+DEPS = [source for _, sources in EVERY_TARGET for source in sources] + [
+    CSRC / "pz_physics.hpp", CSRC / "pz_packed.hpp", CSRC / "pz_memory.hpp", CSRC / "pz_step_io.hpp", CSRC / "pz_diagnostic.hpp", CSRC / "pz_dispatch.hpp",
     CSRC / "pz_policy_rows.hpp", CSRC / "pz_mlp_tile.hpp", CSRC / "pz_traj_scan.hpp", INCLUDE / "pikazoo_hip.h", INCLUDE / "pikazoo_diag.h", INCLUDE / "pikazoo_learn.h",
     INCLUDE / "pikazoo_policy.h", INCLUDE / "pikazoo_ppo.h", INCLUDE / "pikazoo_net.h", INCLUDE / "pikazoo_netgrad.h",
     INCLUDE / "pikazoo_optim.h", INCLUDE / "pikazoo_batch.h", INCLUDE / "pikazoo_pool.h", INCLUDE / "pikazoo_league.h", INCLUDE / "pikazoo_act.h",
-    INCLUDE / "pikazoo_pool_act.h", INCLUDE / "pikazoo_ego.h", INCLUDE / "pikazoo_vtrace.h"]
+    INCLUDE / "pikazoo_pool_act.h", INCLUDE / "pikazoo_ego.h", INCLUDE / "pikazoo_vtrace.h", INCLUDE / "pikazoo_rollout.h"]
 ARCH = "gfx950"
 # the step kernels' six leading arguments (11 dwords) are preloaded into SGPRs at wave launch (pz_kernels.hip: HotArgs)
 FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
@@ -127,7 +134,7 @@ def library_id(lib: Path = LIB):
 
 
 def needs_build() -> bool:
-    return any(library_id(lib) != source_id() for lib, _ in LIBRARY_TARGETS)
+    return any(library_id(lib) != source_id() for lib, _ in EVERY_TARGET)
 
 
 def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
@@ -143,16 +150,16 @@ def _compile(out: Path, sources, extra_flags, verbose: bool) -> None:
 
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
     """The product library (returned) with the diagnostics, the learning, the policy, the PPO, the net, the net-gradient, the
-    optimizer, the batch, the pool, the league, the act, the pool-act, the ego and the V-trace library beside it: each is compiled when it is missing or stale,
+    optimizer, the batch, the pool, the league, the act, the pool-act, the ego, the V-trace and the rollout library beside it: each is compiled when it is missing or stale,
     the compiles side by side (a cold build takes about as long as the product library alone: some three minutes; an
-    up-to-date tree costs fifteen file reads)."""
+    up-to-date tree costs sixteen file reads)."""
     if any("PZ_DIAGNOSTIC_BUILD" in f for f in extra_flags):
         # csrc/pz_diagnostic.hpp: the one compile-time switch of the kernels -- tools/ab.py builds such variants into
         # tools/bin/; the product path never holds one (and _native.load() would refuse its build id "diagnostic")
         raise ValueError("a diagnostic build (-DPZ_DIAGNOSTIC_BUILD) is never written to the product library's path")
     want = source_id(tuple(extra_flags))
     LIB_DIR.mkdir(parents=True, exist_ok=True)
-    todo = [(out, sources) for out, sources in LIBRARY_TARGETS if force or extra_flags or library_id(out) != want]
+    todo = [(out, sources) for out, sources in EVERY_TARGET if force or extra_flags or library_id(out) != want]
     if len(todo) > 1:
         from concurrent.futures import ThreadPoolExecutor
 

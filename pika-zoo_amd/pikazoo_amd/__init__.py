@@ -41,16 +41,19 @@
 
     from pikazoo_amd import vtrace                     # V-trace targets for off-policy samples (learn.gae's bits on-policy), one launch
     out = vtrace.targets(rewards, values_now, terminations, stored_log_probs, log_probs_now, gamma=0.99, lam=0.95)
+
+    from pikazoo_amd import rollout                    # k policy steps -- net, draw and frame -- in one launch: the rollout buffer
+    buf = env.rollout_policy(model, k=32, seed=7, step=env.steps_done)    # the bits of k x (model.act_sample + env.step)
 """
 from ._version import VERSION, __version__  # noqa: F401
 
-__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace"]
+__all__ = ["VERSION", "__version__", "learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace", "rollout"]
 
 
 def __getattr__(name):
-    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` / `pikazoo_amd.ego` / `pikazoo_amd.vtrace` on first use:
+    # `pikazoo_amd.learn` / `pikazoo_amd.policy` / `pikazoo_amd.ppo` / `pikazoo_amd.net` / `pikazoo_amd.netgrad` / `pikazoo_amd.optim` / `pikazoo_amd.batch` / `pikazoo_amd.pool` / `pikazoo_amd.league` / `pikazoo_amd.act` / `pikazoo_amd.pool_act` / `pikazoo_amd.ego` / `pikazoo_amd.vtrace` / `pikazoo_amd.rollout` on first use:
     # importing the package (and with it the step path) never loads those libraries
-    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace"):
+    if name in ("learn", "policy", "ppo", "net", "netgrad", "optim", "batch", "pool", "league", "act", "pool_act", "ego", "vtrace", "rollout"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

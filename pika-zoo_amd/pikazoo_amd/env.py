@@ -1095,6 +1095,30 @@ class raw_env(ParallelEnv):
                 self._poll_action_faults()  # read one call later (no synchronisation here)
         return self._finish_trajectory(out)
 
+    def rollout_policy(self, params_or_model, k: int, seed: int, step=0, first_game: int = 0, activation: str = "tanh",
+                       action_dtype=torch.int64, entropy: bool = False, out: Optional[dict] = None):
+        """``k`` POLICY STEPS in ONE launch (``pz_rollout_policy``): per step the policy net's forward on the current
+        observation rows of both agents, one sampled action each, and the frame on those two actions -- bit for bit what
+        ``k`` iterations of ``model.act_sample(obs, seed, step + t)`` followed by ``env.step(actions)`` return, plus
+        ``model.act`` on the last observations for the bootstrap value.  The state is read and written once; a game that
+        ends is reset in place inside the launch (``auto_reset``), or stays frozen.
+
+        ``params_or_model``: a ``net.ActorCritic`` (its activation is used) or a parameter sequence ``(W1, b1, W2, b2, W3,
+        b3)`` for both agents, or an ``{agent: ...}`` dict with one per agent; the net has 35 inputs, hidden 32 / 64 / 128
+        and ``n_actions + 1`` outputs (hidden 128 with separate weights does not fit the LDS: ``ValueError``).  ``seed``,
+        ``step`` (an int, or a 1-element int64 / uint64 device tensor the launch reads: a caller that replays a captured
+        graph adds ``k`` to it between replays), ``first_game`` and ``action_dtype`` as in ``act.sample``.
+
+        Returns ``obs`` ``{agent: [k + 1, N, 35]}``, ``actions``, ``log_probs``, ``rewards`` ``{agent: [k, N]}``, ``values``
+        ``{agent: [k + 1, N]}`` (row k: the bootstrap), ``terminations`` ``bool[k, N]`` and, with ``entropy=True``,
+        ``entropy`` ``{agent: [k, N]}``: what ``learn.gae`` and ``ppo.loss`` read.  ``out=`` a previous result makes the
+        call allocation-free.  ``steps_done`` grows by k; the launch goes to the current stream without a synchronisation.
+        Human vs human, ``frame_skip=1``, the int32 state and 4-byte rows only; ``k > 1`` needs ``num_envs % 4 == 0``."""
+        from . import rollout  # (a library of its own: nothing loads it before)
+
+        return rollout.policy_rollout(self, params_or_model, k, seed, step=step, first_game=first_game, activation=activation,
+                                      action_dtype=action_dtype, entropy=entropy, out=out)
+
     def _alloc_trajectory(self, k):
         """The output tensors of a k-frame launch; the two observation tensors in different ranks of the device
         memory when they are large enough for that to matter (placement.alloc_pair)."""

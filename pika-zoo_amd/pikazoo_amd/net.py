@@ -236,6 +236,13 @@ class ActorCritic(torch.nn.Module):
             return act.sample(obs, self.parameter_tensors(), self.num_actions, seed, step=step, first_game=first_game,
                               activation=self.activation, head=head, out=out)
 
+    def rollout(self, env, k: int, seed: int, step=0, first_game: int = 0, action_dtype=torch.int64, entropy: bool = False, out=None):
+        """``k`` steps of :meth:`act_sample` and ``env.step`` in ONE launch, both agents on this module's parameters:
+        ``env.unwrapped.rollout_policy(self, k, seed, ...)`` (documented there; nothing loads libpikazoo_rollout.so before)"""
+        with torch.no_grad():
+            return env.unwrapped.rollout_policy(self, k, seed, step=step, first_game=first_game, action_dtype=action_dtype,
+                                                entropy=entropy, out=out)
+
     def evaluate(self, obs):
         """the ``[N, num_actions + 1]`` float32 head of a tensor or an ``{agent: tensor}`` dict of observations, as
         :meth:`act` computes it, differentiable with respect to this module's parameters: ``netgrad.head`` (imported on
