@@ -113,11 +113,11 @@ def restate_float32(obs, params, activation, order=None, mutant=None):
 
 def worst_share(have, ref, tol):
     """(the largest |have - ref| / tol over the elements, the share of rows with an element beyond its tolerance); a NaN on
-    one side alone counts as infinite"""
+    one side alone counts as infinite, -inf on both sides (a -inf mask in b3) as no error; +inf stays an error"""
     have, ref = np.asarray(have, np.float64), np.asarray(ref, np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
         share = np.abs(have - ref) / tol
-    both = np.isnan(have) & np.isnan(ref)
+    both = (np.isnan(have) & np.isnan(ref)) | (np.isneginf(ref) & np.isneginf(have))
     share = np.where(both, 0.0, np.where(np.isnan(share), np.inf, share))
     return float(share.max()) if share.size else 0.0, float((share > 1).any(axis=1).mean()) if share.size else 0.0
 

@@ -8,7 +8,8 @@ equality, one axis swept per test.  (2) Independent of the older kernels: the C 
 reported, reproduces the observations, rewards, flags and the final state, and the float64 judge of tests/act_judge.py passes
 each slab's (observations, action, log-prob, entropy, value) within its own derived tolerance and ambiguity width.  One case
 goes through the C ABI with every output between sentinel guards -- in front, behind and in the pad rows of every slab -- and
-NaN patterns around the parameters.
+NaN patterns around the parameters.  The sweep over the launch's runtime configurations, from planted states, lives in
+tests/test_gpu_policy_rollout_configs.py (its cases: tests/policy_rollout_configs.py).
 """
 import sys
 from pathlib import Path
